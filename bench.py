@@ -10,11 +10,15 @@ main_pretrain.py:213-245) on synthetic batches.  Default = BASELINE.json's headl
     python bench.py --clip ViT-B/16 --frames 24 --batch 16            # one rank's share of SURVEY config 5
     python bench.py --regime fp32                                     # the reference's model.float() recipe: the regime held to 1e-3
     python bench.py --gpus N --steps K --warmup W                     # starts its own N ranks (children, torch.distributed.run)
+    python bench.py --full                                            # + rooflines, unfolded-kernel steps, ViT forward, CPU baseline
+    python bench.py --steps 10 --dump-outputs DIR                     # + the last timed step's outputs as DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 `--batch` is the GLOBAL batch (the reference's --batch_size semantics, dataloaders/dataloader.py:84), split
-over ranks: strong scaling.  Rank 0 prints ONE JSON line.
+over ranks: strong scaling.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times --steps steps and reports
+them (`value`, `ms_per_step`); the records that take runs of their own (roofline, roofline_hbm, vit_forward, comm,
+ms_per_step_unfolded, cpu_baseline) are measured with --full only and are null (cpu_baseline: absent) without it.
 """
 import argparse
 import json
@@ -87,27 +91,31 @@ def eval_leg(args, dev):
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
     ops.raise_on_device_errors()
-    # the scorer alone, HIP events on the launch stream
-    packed = ops.eval_pack(torch.cat(vs).float().contiguous(), torch.cat(us).float().contiguous())
-    qn, _ = ops.l2norm_fwd(torch.cat(qs).float().contiguous())
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    launches = 0
-    e0.record()
-    for _ in range(args.steps):
-        for s0 in range(0, nq, 4096):
-            ops.eval_score(qn[s0:s0 + 4096], packed, nv, F, model.top_frames, 100.0, want=("score",))
-            launches += 1
-    e1.record()
-    torch.cuda.synchronize()
-    us_launch = e0.elapsed_time(e1) * 1e3 / launches
-    flops = 2.0 * nq * nv * (F + 1) * E / (launches / args.steps)
-    slots = ops.eval_slots(F)
-    roof = {"bound": "mfma", "kernel": "gemm_f32_kernel<..., TOPK> (exact-f32 MFMA scorer with the top-k epilogue)",
-            "achieved": round(flops / us_launch / 1e6, 1), "peak": 157.0, "unit": "TFLOP/s",
-            "frac": round(flops / us_launch / 1e6 / 157.0, 4), "traffic": None,
-            "avg_launch_us": round(us_launch, 1), "launches_per_step": launches // args.steps,
-            "note": f"useful FLOPs 2 nq nv (F+1) 512; the kernel multiplies {slots} slots per video (padding: x{slots / (F + 1):.2f}); "
-                    f"algorithmic HBM bytes {(nq * E + nv * (F + 1) * E + nq * nv) * 4 / 1e6:.0f} MB per step: not HBM-bound"}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"sim": sim})
+    roof = None
+    if args.full:
+        # the scorer alone, HIP events on the launch stream
+        packed = ops.eval_pack(torch.cat(vs).float().contiguous(), torch.cat(us).float().contiguous())
+        qn, _ = ops.l2norm_fwd(torch.cat(qs).float().contiguous())
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        launches = 0
+        e0.record()
+        for _ in range(args.steps):
+            for s0 in range(0, nq, 4096):
+                ops.eval_score(qn[s0:s0 + 4096], packed, nv, F, model.top_frames, 100.0, want=("score",))
+                launches += 1
+        e1.record()
+        torch.cuda.synchronize()
+        us_launch = e0.elapsed_time(e1) * 1e3 / launches
+        flops = 2.0 * nq * nv * (F + 1) * E / (launches / args.steps)
+        slots = ops.eval_slots(F)
+        roof = {"bound": "mfma", "kernel": "gemm_f32_kernel<..., TOPK> (exact-f32 MFMA scorer with the top-k epilogue)",
+                "achieved": round(flops / us_launch / 1e6, 1), "peak": 157.0, "unit": "TFLOP/s",
+                "frac": round(flops / us_launch / 1e6 / 157.0, 4), "traffic": None,
+                "avg_launch_us": round(us_launch, 1), "launches_per_step": launches // args.steps,
+                "note": f"useful FLOPs 2 nq nv (F+1) 512; the kernel multiplies {slots} slots per video (padding: x{slots / (F + 1):.2f}); "
+                        f"algorithmic HBM bytes {(nq * E + nv * (F + 1) * E + nq * nv) * 4 / 1e6:.0f} MB per step: not HBM-bound"}
     out = {"metric": f"query-video pairs scored/sec, eval leg {nq} x {nv} x F={F} (top-{model.top_frames} frames)",
            "value": round(nq * nv / dt, 1), "unit": "query-video pairs/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": round(dt * 1e3, 3), "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
@@ -115,7 +123,7 @@ def eval_leg(args, dev):
            "config": {"workload": f"cached-feature retrieval scoring, {nq} queries x {nv} videos x {F} frames, 512-d fp32 features "
                                   f"(concatenate + normalise + pack + score)", "mode": "eval"},
            "roofline": roof, "checksum": round(float(sim.double().sum()), 3)}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         sys.path.insert(0, ROOT)
         import oracle.hmmc_oracle as O
         n_s = min(nq, 1500)
@@ -134,6 +142,34 @@ def eval_leg(args, dev):
                                "sample": f"oracle eval_scores on {n_s} of the queries x {nv} videos x {F} frames, {t:.2f} s, {_cpu_model()}"}
         out["max_abs_err_vs_oracle_sample"] = float((sim[:n_s] - ref.to(dev)).abs().max())
     print(json.dumps(out), flush=True)
+
+
+DUMP_BYTES_MAX = 64 * 2 ** 20
+DUMP_SAMPLE = {"sim": 2 ** 22}          # most elements written of one array (a fixed sample of a larger one); others: DUMP_SAMPLE_DEFAULT
+DUMP_SAMPLE_DEFAULT = 8192
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every tensor of `arrays` as out_dir/<name>.npy, float64 where the tensor is float64 or an integer,
+    float32 otherwise.  An array of more elements than its sample size is replaced by a fixed sample of its flattened
+    elements (indices drawn from a generator seeded with the name, in ascending order), the same in every run and build;
+    a smaller one keeps its shape."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        k = DUMP_SAMPLE.get(name, DUMP_SAMPLE_DEFAULT)
+        if t.numel() > k:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(t.numel(), size=k, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        wide = t.dtype == torch.float64 or not t.is_floating_point()
+        a = t.to(torch.float64 if wide else torch.float32).cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_BYTES_MAX:
+            raise SystemExit(f"--dump-outputs: more than {DUMP_BYTES_MAX >> 20} MB at {name}")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def prep_optimizer(model, cfg, t_total):
@@ -445,8 +481,8 @@ def main():
                          "(tests/test_gpu_fp32_regime.py); roofline against the 157 TFLOP/s exact-f32 MFMA peak")
     ap.add_argument("--unfolded-steps", type=int, default=3,
                     help="fine-tune / pre-train, f16 regime: extra timed steps with HMMC_FOLD_LN=0 HMMC_FOLD_LN_TRAIN=0 - the kernels "
-                         "whose rounding points are the reference's - reported as ms_per_step_unfolded (0: skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                         "whose rounding points are the reference's - reported as ms_per_step_unfolded (0: skip; --full only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--single-stream", action="store_true",
                     help="run everything on one stream (no tower / weight-gradient overlap): the mode whose rocprofv3 "
                          "per-kernel averages are comparable with roofline.avg_launch_us")
@@ -454,12 +490,22 @@ def main():
                     help="compute units kept out of the GEMM grids for RCCL (default: 16 when --gpus > 1, else 0); "
                          "giving it with --gpus 1 measures what the reservation costs")
     ap.add_argument("--roofline-steps", type=int, default=3,
-                    help="extra single-stream steps after the timed region over which the GEMM launches are timed with HIP events")
+                    help="extra single-stream steps after the timed region over which the GEMM launches are timed with HIP events (--full only)")
     ap.add_argument("--no-hbm-roofline", action="store_true",
                     help="skip the roofline_hbm leg (its stand-alone LayerNorm / attention / optimizer launches would otherwise sit in a "
-                         "kernel trace of this command)")
-    ap.add_argument("--vit-forward-iters", type=int, default=5, help="timed frame-encoder forward passes for the vit_forward record (0: skip)")
+                         "kernel trace of this --full command)")
+    ap.add_argument("--vit-forward-iters", type=int, default=5, help="timed frame-encoder forward passes for the vit_forward record (0: skip; --full only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beside the headline figure: the unfolded-kernel steps, "
+                         "the GEMM roofline, the vit_forward and roofline_hbm records, the comm record (N > 1), the eval scorer's "
+                         "roofline and the CPU baseline.  Without it the run sets up, warms up, times --steps steps and reports them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64; a fixed, seeded sample "
+                         "of every large array; under 64 MB in all): the loss, the gradient norm and the model state after the "
+                         "step, or the eval leg's similarity matrix")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.batch is None:
         args.batch = 256 if args.mode == "finetune" else 128
 
@@ -547,10 +593,10 @@ def main():
     def step(i):
         loss = net(*inputs, i)
         loss.backward()
-        clip_grad_norm_(params, 1.0)
+        grad_norm = clip_grad_norm_(params, 1.0)
         optimizer.step()
         optimizer.zero_grad()
-        return loss
+        return loss, grad_norm
 
     for i in range(args.warmup):
         step(i)
@@ -559,7 +605,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        loss = step(args.warmup + i)
+        loss, grad_norm = step(args.warmup + i)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -571,13 +617,19 @@ def main():
     dt = float(t.item())
     final_loss = float(loss.detach())
     ops.raise_on_device_errors()
+    if args.dump_outputs and rank == 0:
+        # before anything below runs another step or touches the optimizer: the state as the last timed step left it
+        outputs = {"loss": loss.detach(), "grad_norm": grad_norm}
+        outputs.update({f"state.{k}": v for k, v in model.state_dict().items()})
+        dump_outputs(args.dump_outputs, outputs)
 
+    # The records below are measured with --full only.
     import hmmc_amd.functional as _fn
     import hmmc_amd.modeling as _md
     # The same step on the unfolded kernels (HMMC_FOLD_LN=0 HMMC_FOLD_LN_TRAIN=0: LayerNorm then GEMM, every rounding point where
     # the reference has it) - the default folds ln_1 / ln_2 of the frame tower into in_proj / c_fc.
     ms_unfolded = None
-    if args.unfolded_steps > 0 and not fp32:
+    if args.full and args.unfolded_steps > 0 and not fp32:
         pol = (_fn._FOLD_LN, _fn._FOLD_LN_TRAIN)
         _fn._FOLD_LN, _fn._FOLD_LN_TRAIN = "0", "0"
         step(args.warmup + args.steps)
@@ -610,7 +662,7 @@ def main():
     # overlapped forward - what several tests do - does, once.)
     del loss
     prof, dt_single = {}, 0.0
-    if args.roofline_steps > 0:                          # (0: nothing after the timed region - kernel traces of the plain loop)
+    if args.full and args.roofline_steps > 0:            # (0: nothing after the timed region - kernel traces of the plain loop)
         import gc
         gc.collect()
         _md._OVERLAP_TOWERS, _fn._WGRAD_STREAM = False, False
@@ -629,7 +681,7 @@ def main():
     # eval mode, timed with events on the current stream; FLOPs in the reference's formulation (all-token final projection)
     fm = flop_model(dims, args.frames, args.length)
     vit_forward = None
-    if args.vit_forward_iters > 0 and not fp32:
+    if args.full and args.vit_forward_iters > 0 and not fp32:
         frames_flat = video.view(b * args.frames, 3, res, res)
         enc = model.visual_encoder
 
@@ -657,42 +709,45 @@ def main():
                                "points follow the reference's. frac_of_mfma_peak counts the FLOPs this path executes (last block's "
                                "per-token half and the projection on the class token only), the reference-formulation figure "
                                "counts the reference's"}
-    hbm = hbm_rooflines(dev, b, args.frames, dims, params, optimizer, model, pretrain) if world == 1 and not args.no_hbm_roofline else None
-    comm = comm_leg(args, dev, model, net, params, step, b, args.frames) if world > 1 else None
+    full1 = args.full and world == 1
+    hbm = hbm_rooflines(dev, b, args.frames, dims, params, optimizer, model, pretrain) if full1 and not args.no_hbm_roofline else None
+    comm = comm_leg(args, dev, model, net, params, step, b, args.frames) if args.full and world > 1 else None
 
     if rank == 0:
         ms = dt / args.steps * 1e3
         value = args.batch * args.steps / dt
-        # the dominant kernel family: the fp16 GEMM (three operand layouts) as built, the exact-fp32 GEMM in the fp32 regime
-        f32_prof = prof.pop("f32", None)
-        if fp32:
-            prof = {"f32": f32_prof} if f32_prof else {}
         peak = MFMA_F32_PEAK_TFLOPS if fp32 else MFMA_PEAK_TFLOPS
-        flops = sum(p["flops"] for p in prof.values())
-        secs = sum(p["seconds"] for p in prof.values())
-        launches = sum(p["launches"] for p in prof.values())
-        achieved = flops / secs / 1e12 if secs > 0 else 0.0
-        lps = launches // max(args.roofline_steps, 1)
-        roof = {"bound": "mfma", "kernel": ("gemm_f32_*kernel (exact-f32 MFMA 16x16x4 GEMM, all orientations and tile kernels)" if fp32 else
-                                            "gemm_f16_kernel (fp16 MFMA GEMM, all operand layouts)"),
-                "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
-                "frac": round(achieved / peak, 4), "traffic": None, "traffic_unit": "bytes/launch",
-                "launches_per_step": lps,
-                "avg_launch_us": round(secs / max(launches, 1) * 1e6, 2),
-                "measured_over": f"{args.roofline_steps} single-stream steps after the timed region "
-                                 f"({dt_single / max(args.roofline_steps, 1) * 1e3:.2f} ms/step without the stream overlap)",
-                "gemm_share_of_step": round(secs / dt_single, 4) if dt_single > 0 else None,
-                "algorithmic_bytes_per_launch": round(sum(p.get("bytes", 0) for p in prof.values()) / max(launches, 1)) or None,
-                "by_layout": {k: {"tflops": round(p["flops"] / p["seconds"] / 1e12, 1), "launches": p["launches"],
-                                  "avg_us": round(p["seconds"] / p["launches"] * 1e6, 2)} for k, p in prof.items()}}
-        if fp32:
-            roof["traffic_source"] = "not collected for the fp32 regime"
-        else:
-            roof["traffic"], roof["traffic_source"] = recorded_traffic(args, b, lps)
-            if f32_prof:
-                roof["gemm_f32_beside_it"] = {"tflops": round(f32_prof["flops"] / f32_prof["seconds"] / 1e12, 1), "launches": f32_prof["launches"] // max(args.roofline_steps, 1),
-                                              "ms_per_step": round(f32_prof["seconds"] / max(args.roofline_steps, 1) * 1e3, 3),
-                                              "note": "hmmc_gemm_f32 launches of the same steps (temporal transformer, heads): exact-f32 MFMA, peak 157"}
+        roof = None
+        if args.full:
+            # the dominant kernel family: the fp16 GEMM (three operand layouts) as built, the exact-fp32 GEMM in the fp32 regime
+            f32_prof = prof.pop("f32", None)
+            if fp32:
+                prof = {"f32": f32_prof} if f32_prof else {}
+            flops = sum(p["flops"] for p in prof.values())
+            secs = sum(p["seconds"] for p in prof.values())
+            launches = sum(p["launches"] for p in prof.values())
+            achieved = flops / secs / 1e12 if secs > 0 else 0.0
+            lps = launches // max(args.roofline_steps, 1)
+            roof = {"bound": "mfma", "kernel": ("gemm_f32_*kernel (exact-f32 MFMA 16x16x4 GEMM, all orientations and tile kernels)" if fp32 else
+                                                "gemm_f16_kernel (fp16 MFMA GEMM, all operand layouts)"),
+                    "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
+                    "frac": round(achieved / peak, 4), "traffic": None, "traffic_unit": "bytes/launch",
+                    "launches_per_step": lps,
+                    "avg_launch_us": round(secs / max(launches, 1) * 1e6, 2),
+                    "measured_over": f"{args.roofline_steps} single-stream steps after the timed region "
+                                     f"({dt_single / max(args.roofline_steps, 1) * 1e3:.2f} ms/step without the stream overlap)",
+                    "gemm_share_of_step": round(secs / dt_single, 4) if dt_single > 0 else None,
+                    "algorithmic_bytes_per_launch": round(sum(p.get("bytes", 0) for p in prof.values()) / max(launches, 1)) or None,
+                    "by_layout": {k: {"tflops": round(p["flops"] / p["seconds"] / 1e12, 1), "launches": p["launches"],
+                                      "avg_us": round(p["seconds"] / p["launches"] * 1e6, 2)} for k, p in prof.items()}}
+            if fp32:
+                roof["traffic_source"] = "not collected for the fp32 regime"
+            else:
+                roof["traffic"], roof["traffic_source"] = recorded_traffic(args, b, lps)
+                if f32_prof:
+                    roof["gemm_f32_beside_it"] = {"tflops": round(f32_prof["flops"] / f32_prof["seconds"] / 1e12, 1), "launches": f32_prof["launches"] // max(args.roofline_steps, 1),
+                                                  "ms_per_step": round(f32_prof["seconds"] / max(args.roofline_steps, 1) * 1e3, 3),
+                                                  "note": "hmmc_gemm_f32 launches of the same steps (temporal transformer, heads): exact-f32 MFMA, peak 157"}
         if pretrain:
             c4 = (args.clip == "ViT-B/32" and args.frames == 12 and args.title_length == 45 and args.tag_length == 25)
             per_pair, per_pair_exec = (FLOP_PER_PAIR_PRETRAIN_C4 if c4 else None), None
@@ -726,7 +781,7 @@ def main():
                                              "(frame tower's ln_1 / ln_2 folded into in_proj / c_fc)") if ms_unfolded else None,
                "final_loss": round(final_loss, 4), "roofline": roof, "roofline_hbm": hbm, "comm": comm, "vit_forward": vit_forward,
                "peak_device_memory_gib": round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 2)}
-        if world == 1 and not args.no_cpu_baseline:
+        if full1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(12, 32)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -1,6 +1,6 @@
 for args in "" "--mode pretrain" "--batch 128" "--batch 64" "--batch 32" "--clip ViT-B/16 --frames 24 --batch 16"; do
   echo "== $args"
-  python bench.py --no-cpu-baseline $args 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline $args 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']; v=d.get('vit_forward') or {}

@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 run_stats() {   # name, bench args...
   local name=$1; shift
   rm -rf /tmp/prof_$name
-  rocprofv3 --kernel-trace --stats -d /tmp/prof_$name -o t --output-format csv -- python3 $R/bench.py --no-cpu-baseline --no-hbm-roofline --unfolded-steps 0 "$@" > $OUT/$name.log 2>&1
+  rocprofv3 --kernel-trace --stats -d /tmp/prof_$name -o t --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline --no-hbm-roofline --unfolded-steps 0 "$@" > $OUT/$name.log 2>&1
   cp $(find /tmp/prof_$name -name "*kernel_stats.csv" | head -1) $OUT/$name.csv
   echo "$name: $(tail -1 $OUT/$name.log | cut -c1-160)"
 }
@@ -48,5 +48,5 @@ ls -la $OUT
 # eval leg (fused scorer): kernel stats of bench.py --mode eval
 cd /tmp
 rm -rf /tmp/prof_eval
-rocprofv3 --kernel-trace --stats -d /tmp/prof_eval -o t --output-format csv -- python3 $R/bench.py --mode eval --frames 24 --no-cpu-baseline > $OUT/${TAG}_bench_eval_f24_kernel_stats.log 2>&1
+rocprofv3 --kernel-trace --stats -d /tmp/prof_eval -o t --output-format csv -- python3 $R/bench.py --mode eval --frames 24 --full --no-cpu-baseline > $OUT/${TAG}_bench_eval_f24_kernel_stats.log 2>&1
 cp $(find /tmp/prof_eval -name "*kernel_stats.csv" | head -1) $OUT/${TAG}_bench_eval_f24_kernel_stats.csv

@@ -374,7 +374,7 @@ def test_bench_self_launches_two_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["HMMC_BENCH_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--batch", "8", "--frames", "4", "--steps", "2",
-                        "--warmup", "1", "--roofline-steps", "1", "--vit-forward-iters", "1", "--no-cpu-baseline"],
+                        "--warmup", "1", "--full", "--roofline-steps", "1", "--vit-forward-iters", "1", "--no-cpu-baseline"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -396,3 +396,4 @@ def test_bench_self_launches_two_ranks():
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert out["scaling"] == "weak" and out["config"]["per_gpu_batch"] == 4 and out["config"]["global_batch"] == 8
+    assert out["roofline"] is None and out["comm"] is None          # without --full: the timed steps and nothing after them

@@ -498,6 +498,13 @@ class MlpFn(torch.autograd.Function):
         else:
             n = float(h.shape[0])
         rm, rv, nbt, mom = running if running is not None else (None, None, None, 0.0)
+        if mom is None:                                  # nn.BatchNorm1d(momentum=None): cumulative average, factor 1 / batches seen
+            if rm is None:
+                mom = 0.0                                # no running statistics to update
+            elif nbt is None:
+                raise ValueError("BatchNorm1d(momentum=None) keeps a cumulative average: it needs num_batches_tracked")
+            else:
+                mom = 1.0 / (float(nbt) + 1.0)           # a host read of the counter, as nn.BatchNorm1d does; hmmc_bn_finalize adds 1
         mean, var, rstd = ops.bn_finalize(sums, n, eps, mom, rm, rv, nbt)        # one launch: statistics + running statistics
         y = ops.bn_apply_relu(h, mean, rstd, gamma, beta)
         out = ops.linear_f32(y, w2, bias=b2)

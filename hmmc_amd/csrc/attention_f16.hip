@@ -376,9 +376,6 @@ __global__ __launch_bounds__(64 * BWD_WPB, 2) void attn_bwd_kernel(AttnArgs p) {
 
 }  // namespace
 
-int hmmc_attention_long_fwd(const AttnArgs& p, hipStream_t stream, bool lead = false);
-int hmmc_attention_long_bwd(const AttnArgs& p, hipStream_t stream, bool lead = false);
-
 extern "C" int hmmc_attention_f16_fwd(const void* qkv, void* out, float* lse, int nseq, int L, int H, int causal,
                                       hipStream_t stream) {
   if (!qkv || !out || !lse || nseq <= 0 || L <= 0 || H <= 0) return HMMC_ERR_ARG;

@@ -13,6 +13,10 @@ struct HmmcAttnArgs {
 };
 typedef HmmcAttnArgs AttnArgs;
 
+// sequences of 65..256 tokens (attention_long_f16.hip); lead: query 0 of every sequence only (hmmc_attention_f16_fwd_lead)
+int hmmc_attention_long_fwd(const AttnArgs& p, hipStream_t stream, bool lead = false);
+int hmmc_attention_long_bwd(const AttnArgs& p, hipStream_t stream, bool lead = false);
+
 namespace {
 
 constexpr int DH = 64;          // head dim of every CLIP tower

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "hmmc_hip.h"   // every entry point is defined against its declaration there
 
 typedef _Float16 half_t;
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
@@ -14,11 +15,11 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 
 #define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 
-#define HMMC_OK 0
-#define HMMC_ERR_ARG (-1)
-#define HMMC_ERR_UNSUPPORTED (-2)
-#define HMMC_ERR_WORKSPACE (-3)
-#define HMMC_ERR_LAUNCH (-4)
+// the epilogue flags of hmmc_gemm_f16 / hmmc_gemm_f32 (include/hmmc_hip.h) under short names
+enum HmmcEpilogue { EPI_BIAS = HMMC_EPI_BIAS, EPI_RESID = HMMC_EPI_RESID, EPI_QGELU = HMMC_EPI_QGELU, EPI_DGELU = HMMC_EPI_DGELU,
+                   EPI_RELU = HMMC_EPI_RELU, EPI_COLSUM = HMMC_EPI_COLSUM, EPI_SAVE_DGELU = HMMC_EPI_SAVE_DGELU,
+                   EPI_MULAUX = HMMC_EPI_MULAUX, EPI_LNFOLD = HMMC_EPI_LNFOLD, EPI_ROWSTAT = HMMC_EPI_ROWSTAT,
+                   EPI_ROWSCALE = HMMC_EPI_ROWSCALE };
 
 static inline int hmmc_launch_status() {
   hipError_t e = hipGetLastError();

@@ -45,11 +45,6 @@ namespace {
 
 constexpr int BKT = 64;
 
-enum { EPI_BIAS = 1, EPI_RESID = 2, EPI_QGELU = 4, EPI_DGELU = 8, EPI_COLSUM = 32, EPI_SAVE_DGELU = 64, EPI_MULAUX = 128,
-       EPI_LNFOLD = 256,      // acc -> a_r * acc + (b_r * c_n + d_n): LayerNorm folded into the GEMM (rowstat, colterms), see below
-       EPI_ROWSTAT = 512,     // + per-row (sum, sum of squares) of the fp16 values written, one pair per 64-column block (stat_part)
-       EPI_ROWSCALE = 1024 }; // out *= rowstat[m][0] (the row's rstd) as the last step: the backward of a folded LayerNorm (ln_fold.hip)
-
 struct GemmArgs {
   const half_t* A; const half_t* B; half_t* C;
   const half_t* bias; const half_t* resid; half_t* aux_out; const half_t* aux_in;

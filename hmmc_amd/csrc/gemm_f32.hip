@@ -18,8 +18,6 @@ namespace {
 constexpr int TM = 64, TN = 64, TK = 16;
 constexpr int LDS_LD = 80;   // floats per k-row: 64 + 16 keeps the two k-rows of a 32-lane half on disjoint banks
 
-enum { EPI_BIAS = 1, EPI_RESID = 2, EPI_QGELU = 4, EPI_DGELU = 8, EPI_RELU = 16 };
-
 struct G32 {
   const float* A; const float* B; float* C; const float* bias; const float* resid; float* aux_out; const float* aux_in;
   int M, N, K; long sam, sak, sbk, sbn; int ldc; float alpha; int flags; int avec, bvec, cvec;

@@ -658,9 +658,8 @@ __global__ __launch_bounds__(256) void cast_kernel(const TI* __restrict__ in, TO
 // None of their sums is needed before the tower's backward returns, so instead of a 5 us reduce launch after each producer -
 // ~100 launches per step on the critical path of the backward, 1.6 ms of a 17 ms step at 32 videos per GPU - the producers
 // write into per-layer slots and ONE launch reduces all of them.  Task t: out_s[c % seg] = sum_r partial[r][c], s = c / seg.
-struct ReduceTask { const float* partial; int R, N, seg; void* out[3]; int dtype[3]; };
 constexpr int REDUCE_MAX_TASKS = 48;
-struct ReduceArgs { ReduceTask t[REDUCE_MAX_TASKS]; int off[REDUCE_MAX_TASKS + 1]; int n; };
+struct ReduceArgs { HmmcReduceTask t[REDUCE_MAX_TASKS]; int off[REDUCE_MAX_TASKS + 1]; int n; };
 
 // A block takes 128 columns of one task (32 lanes x 4 columns: 512 contiguous bytes per row and 32-lane group) and its 8 row
 // lanes walk the rows with four independent 16-byte loads in flight each (round 5; one column per thread and two loads in flight
@@ -671,7 +670,7 @@ __global__ __launch_bounds__(256) void multi_colreduce_kernel(ReduceArgs a) {
   __shared__ f4 red[8][33];
   int ti = 0;
   while (ti + 1 < a.n && (int)blockIdx.x >= a.off[ti + 1]) ++ti;           // block-uniform
-  const ReduceTask& t = a.t[ti];
+  const HmmcReduceTask& t = a.t[ti];
   const int c = threadIdx.x & 31, rl = threadIdx.x >> 5;
   const int col = ((int)blockIdx.x - a.off[ti]) * MCR_COLS + 4 * c;
   const float* P = t.partial;
@@ -966,16 +965,15 @@ extern "C" int hmmc_cast(const void* in, void* out, long n, int kind, hipStream_
   return hmmc_launch_status();
 }
 
-// tasks: HOST array of {partial, R, N, seg, out[3], dtype[3]} (layout of struct HmmcReduceTask in include/hmmc_hip.h)
-extern "C" int hmmc_multi_colreduce(const void* tasks_host, int ntasks, hipStream_t stream) {
-  if (!tasks_host || ntasks <= 0) return HMMC_ERR_ARG;
-  const ReduceTask* tk = (const ReduceTask*)tasks_host;
+// tk: HOST array of tasks
+extern "C" int hmmc_multi_colreduce(const HmmcReduceTask* tk, int ntasks, hipStream_t stream) {
+  if (!tk || ntasks <= 0) return HMMC_ERR_ARG;
   for (int base = 0; base < ntasks; base += REDUCE_MAX_TASKS) {
     ReduceArgs a;
     a.n = ntasks - base < REDUCE_MAX_TASKS ? ntasks - base : REDUCE_MAX_TASKS;
     int blocks = 0;
     for (int i = 0; i < a.n; ++i) {
-      const ReduceTask& t = tk[base + i];
+      const HmmcReduceTask& t = tk[base + i];
       if (!t.partial || t.R <= 0 || t.N <= 0 || t.seg <= 0 || (t.N + t.seg - 1) / t.seg > 3) return HMMC_ERR_ARG;
       a.t[i] = t;
       a.off[i] = blocks;

@@ -16,52 +16,7 @@
 #include <utility>
 #include <vector>
 
-extern "C" {
-int hmmc_gemm_f16(const void*, const void*, void*, int, int, int, int, int, int, int, int, const void*, const void*, void*,
-                  const void*, int, void*, size_t, hipStream_t);
-size_t hmmc_gemm_f16_workspace(int, int, int);
-int hmmc_gemm_f32(const float*, const float*, float*, int, int, int, long, long, long, long, int, float, const float*,
-                  const float*, float*, const float*, int, hipStream_t);
-int hmmc_layernorm_fwd(const void*, const float*, const float*, void*, float*, float*, const int*, int, int, long, float, int,
-                       hipStream_t);
-int hmmc_layernorm_bwd(const void*, const void*, const float*, const float*, const float*, const void*, void*, float*, float*,
-                       void*, const int*, int, int, long, int, void*, size_t, hipStream_t);
-size_t hmmc_layernorm_bwd_workspace(int, int);
-int hmmc_layernorm_bwd_rows(int);
-int hmmc_layernorm_bwd_partial(const void*, const void*, const float*, const float*, const float*, const void*, void*, float*, int,
-                               const int*, int, int, long, int, hipStream_t);
-int hmmc_multi_colreduce(const void*, int, hipStream_t);
-int hmmc_colsum(const void*, void*, int, int, long, int, int, int, void*, size_t, hipStream_t);
-size_t hmmc_colsum_workspace(int, int);
-int hmmc_attention_f16_fwd(const void*, void*, float*, int, int, int, int, hipStream_t);
-int hmmc_attention_f16_bwd(const void*, const void*, const float*, const void*, void*, float*, int, int, int, int, hipStream_t);
-size_t hmmc_gemm_f16_colsum_rows(int, int, int);
-size_t hmmc_gemm_f16_wgrad_group_workspace(const int*, const int*, int, int);
-int hmmc_gemm_f16_wgrad_group(const void* const*, const void* const*, void* const*, float* const*, const int*, const int*, int, int,
-                              void*, size_t, hipStream_t);
-int hmmc_gemm_f16_fold(const void*, const void*, void*, int, int, int, int, int, int, int, const void*, const void*, void*, const void*,
-                       int, const float*, const float*, float*, void*, size_t, hipStream_t);
-int hmmc_ln_fold_prep(const void* const*, const float* const*, const float* const*, const void* const*, void* const*, float* const*,
-                      const int*, int, int, hipStream_t);
-int hmmc_rowstat(const void*, float*, int, int, long, float, hipStream_t);
-int hmmc_rowstat_finalize(const float*, float*, int, int, int, float, hipStream_t);
-int hmmc_attention_f16_fwd_lead(const void* qkv, void* out, float* lse, int nseq, int L, int H, int causal, hipStream_t stream);
-int hmmc_attention_f16_bwd_lead(const void* qkv, const void* out, const float* lse, const void* dout, void* dqkv, float* dbias_partial,
-                                const float* rowstat, int nseq, int L, int H, int causal, hipStream_t stream);
-int hmmc_attention_f16_bwd_scaled(const void*, const void*, const float*, const void*, void*, float*, const float*, int, int, int, int,
-                                  hipStream_t);
-int hmmc_layernorm_bwd_fold_rows(int);
-int hmmc_layernorm_bwd_fold(const void*, const void*, const float*, const void*, void*, float*, int, int, int, long, hipStream_t);
-int hmmc_fold_grad_finish(const float* const*, const void* const*, const float* const*, const float* const*, const void* const*,
-                          void* const*, float* const*, float* const*, float* const*, const int*, int, int, hipStream_t);
-int hmmc_temporal_attention_fwd(const float*, float*, float*, int, int, int, int, hipStream_t);
-int hmmc_temporal_attention_bwd(const float*, const float*, const float*, float*, int, int, int, hipStream_t);
-}
-
 namespace {
-
-enum { EPI_BIAS = 1, EPI_RESID = 2, EPI_QGELU = 4, EPI_DGELU = 8, EPI_COLSUM = 32, EPI_SAVE_DGELU = 64, EPI_MULAUX = 128,
-       EPI_LNFOLD = 256, EPI_ROWSTAT = 512, EPI_ROWSCALE = 1024 };
 
 inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -168,7 +123,6 @@ extern "C" size_t hmmc_tower_bwd_scratch_bytes(long tokens, int D, int fp32) {
 // fp32 partial sums of the fp16 tower's deferred reductions, one slot per layer (hmmc_tower_bwd reduces all of them in one
 // launch at its end): LayerNorm 2 and LayerNorm 1 ([ln rows][3D]: dgamma | dbeta | column sums of dx), the c_fc bias from the
 // QuickGELU' dgrad epilogue [colsum_rows][4D], the in_proj bias from the attention backward [nseq][3D]
-struct ReduceTask { const float* partial; int R, N, seg; void* out[3]; int dtype[3]; };     // = HmmcReduceTask
 struct PartSlot { size_t ln2, ln1, fc, attn, bytes; };
 static PartSlot part_slot(long tokens, int D, int nseq) {
   PartSlot p;
@@ -617,9 +571,9 @@ static int tower_bwd_impl(const void* dy, void* dx, const void* x0, const void* 
   char* const part_base = (char*)workspace + gen;
   void* wws = (char*)workspace + gen + part_bytes;
   // second-stage reductions of the fp16 tower, all in one launch at the end (none of their results is read before)
-  std::vector<ReduceTask> tasks;
+  std::vector<HmmcReduceTask> tasks;
   auto defer = [&](const float* partial, int R, int N, int seg, void* o0, int d0, void* o1 = nullptr, int d1 = 1, void* o2 = nullptr,
-                   int d2 = 1) { tasks.push_back(ReduceTask{partial, R, N, seg, {o0, o1, o2}, {d0, d1, d2}}); };
+                   int d2 = 1) { tasks.push_back(HmmcReduceTask{partial, R, N, seg, {o0, o1, o2}, {d0, d1, d2}}); };
   // LayerNorm backward: fp32 towers reduce at once, fp16 towers leave the partial matrix in the layer's slot
   auto ln_bwd = [&](const void* dyp, const void* xp, const float* gm, const float* mean, const float* rstd, const void* dres,
                     void* dxp, float* dgamma, float* dbeta, void* dx_colsum, int rows, long stride, float* slotp) -> int {

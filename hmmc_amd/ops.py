@@ -11,10 +11,9 @@ import torch
 from . import _lib
 from ._lib import call, ptr, query
 
-EPI_BIAS, EPI_RESID, EPI_QGELU, EPI_DGELU = 1, 2, 4, 8
-EPI_COLSUM = 32
-EPI_SAVE_DGELU, EPI_MULAUX = 64, 128
-EPI_LNFOLD, EPI_ROWSTAT = 256, 512
+# epilogue flags EPI_BIAS, EPI_RESID, EPI_QGELU, EPI_DGELU, EPI_RELU, EPI_COLSUM, EPI_SAVE_DGELU, EPI_MULAUX, EPI_LNFOLD, EPI_ROWSTAT,
+# EPI_ROWSCALE: the HMMC_EPI_* values of include/hmmc_hip.h
+globals().update(_lib.EPI)
 
 _ws_cache = {}
 
@@ -192,7 +191,7 @@ def gemm_f16_rowscaled_dgrad(dy, w, aux, rowstat):
     rows = query("hmmc_gemm_f16_colsum_rows", M, Kp, Np)
     part = torch.empty((rows, Kp), dtype=torch.float32, device=dy.device)
     call("hmmc_gemm_f16_fold", ptr(dy), ptr(w), ptr(c), M, Kp, Np, Np, Kp, Kp, 0, None, None, None, ptr(aux),
-         EPI_MULAUX | EPI_COLSUM | 1024, ptr(rowstat), None, None, ptr(part), part.numel() * 4)
+         EPI_MULAUX | EPI_COLSUM | EPI_ROWSCALE, ptr(rowstat), None, None, ptr(part), part.numel() * 4)
     return c, part
 
 
@@ -480,8 +479,6 @@ def attention_f16_bwd_lead(qkv, lse, dout, nseq, L, H, causal, want_dbias=False,
 
 
 # ----------------------------------------------------------------------------- fp32 side
-
-EPI_RELU = 16
 
 
 def gemm_f32(a, b, M, N, K, sa, sb, alpha=1.0, bias=None, resid=None, aux_in=None, epilogue=0, want_aux=False, out=None):

@@ -7,7 +7,7 @@
  *
  * Conventions: plain device pointers and sizes; the caller owns every buffer (outputs and
  * workspaces are pre-allocated; hmmc_*_workspace() returns the bytes an op needs); kernels are
- * enqueued on `stream` (a hipStream_t) and never synchronise; no device memory is ever allocated.
+ * enqueued on `stream` (hmmc_stream_t: the same type as hipStream_t) and never synchronise; no device memory is ever allocated.
  * Re-entrant across host threads and devices (device properties and LDS opt-ins are kept per
  * device).  Process-wide state, all of it listed here: (1) hmmc_gemm_reserve_cus(n) and the A/B switches
  * of hmmc_set_option, settings; (2) the benchmark timing switch hmmc_gemm_profile_start/stop
@@ -30,13 +30,13 @@
 extern "C" {
 #endif
 
-typedef void* hmmc_stream_t; /* hipStream_t */
+typedef struct ihipStream_t* hmmc_stream_t; /* = hipStream_t; an opaque pointer to C and ctypes */
 
 #define HMMC_OK 0
-#define HMMC_ERR_ARG (-1)
-#define HMMC_ERR_UNSUPPORTED (-2)
-#define HMMC_ERR_WORKSPACE (-3)
-#define HMMC_ERR_LAUNCH (-4)
+#define HMMC_ERR_ARG (-1)         /* invalid argument */
+#define HMMC_ERR_UNSUPPORTED (-2) /* unsupported shape/alignment */
+#define HMMC_ERR_WORKSPACE (-3)   /* workspace too small */
+#define HMMC_ERR_LAUNCH (-4)      /* kernel launch failed */
 
 /* epilogue flags of hmmc_gemm_f16 */
 #define HMMC_EPI_BIAS 1  /* + bias[n]                                   */
@@ -150,7 +150,7 @@ int hmmc_layernorm_bwd_rows(int rows);
 int hmmc_layernorm_bwd_partial(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
                                const void* dres, void* dx, float* partial, int want_dx_colsum, const int* row_index, int rows,
                                int D, long in_stride, int dtype, hmmc_stream_t stream);
-int hmmc_multi_colreduce(const void* tasks, int ntasks, hmmc_stream_t stream);
+int hmmc_multi_colreduce(const HmmcReduceTask* tasks, int ntasks, hmmc_stream_t stream);
 
 /* out[n] = sum_m X[m][n] (bias, class/positional-embedding gradients). dtypes: 0 fp16, 1 fp32. */
 size_t hmmc_colsum_workspace(int M, int N);

@@ -1,51 +1,40 @@
-"""CPU checks of the drop-in boundary: libhmmc_hip.so loads, exports every symbol that
-include/hmmc_hip.h declares, and the ctypes signatures in hmmc_amd/_lib.py match the header."""
-import ctypes
+"""CPU checks of the drop-in boundary: the ctypes signatures hmmc_amd/_lib.py derives from include/hmmc_hip.h cover every
+declaration, and libhmmc_hip.so exports exactly the declared entry points."""
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 
 from conftest import ROOT
 
-HEADER = os.path.join(ROOT, "include", "hmmc_hip.h")
-CODE = {"int": "i", "long": "l", "float": "f", "size_t": "z"}
 
-
-def declared():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    out = {}
-    for m in re.finditer(r"\b(int|size_t)\s+(hmmc_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S):
-        ret, name, args = m.groups()
-        codes = ""
-        for a in [x.strip() for x in args.split(",") if x.strip() and x.strip() != "void"]:
-            if a.startswith("const char*"):
-                codes += "s"
-            elif "*" in a or "hmmc_stream_t" in a:
-                codes += "p"
-            else:
-                codes += CODE[a.split()[-2] if len(a.split()) > 1 else a]
-        out[name] = (codes, CODE[ret])
-    return out
+def test_ctypes_signatures_match_header():
+    from hmmc_amd import _lib
+    src = re.sub(r"/\*.*?\*/", "", open(_lib.HEADER).read(), flags=re.S)
+    names = re.findall(r"\b(hmmc_\w+)\s*\(", src)
+    assert len(names) == len(set(names)) == len(_lib.SIGNATURES), sorted(set(names) ^ set(_lib.SIGNATURES))
+    assert set(names) == set(_lib.SIGNATURES)
+    # pinned signatures guard the parser itself (pointers, long, size_t, const char*, no arguments, non-int returns)
+    assert _lib.SIGNATURES["hmmc_gemm_f16"] == ("pppiiiiiiiippppipzp", "i")
+    assert _lib.SIGNATURES["hmmc_bn_apply_relu"] == ("pppppplip", "i")
+    assert _lib.SIGNATURES["hmmc_set_option"] == ("si", "i")
+    assert _lib.SIGNATURES["hmmc_mt_chunk_elems"] == ("", "i")
+    assert _lib.SIGNATURES["hmmc_tower_workspace_bytes"] == ("liiii", "z")
+    assert _lib.ERRORS == {-1: "invalid argument", -2: "unsupported shape/alignment", -3: "workspace too small",
+                           -4: "kernel launch failed"}
+    from hmmc_amd import ops
+    assert (ops.EPI_BIAS, ops.EPI_RELU, ops.EPI_COLSUM, ops.EPI_ROWSCALE) == (1, 16, 32, 1024) and len(_lib.EPI) == 11
 
 
 def test_library_builds_and_exports_header_symbols():
     from hmmc_amd import build, _lib
     build.build(verbose=False)
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    decl = declared()
-    assert len(decl) >= 10
-    for name in decl:
-        assert hasattr(lib, name), f"{name} declared in hmmc_hip.h but not exported"
-
-
-def test_ctypes_signatures_match_header():
-    from hmmc_amd import _lib
-    decl = declared()
-    assert set(decl) == set(_lib.SIGNATURES), set(decl) ^ set(_lib.SIGNATURES)
-    for name, sig in decl.items():
-        assert _lib.SIGNATURES[name] == sig, (name, _lib.SIGNATURES[name], sig)
+    nm = shutil.which("nm") or "/opt/rocm/llvm/bin/llvm-nm"
+    out = subprocess.run([nm, "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    exported = {line.split()[-1] for line in out.splitlines() if line.split() and line.split()[-1].startswith("hmmc_")}
+    assert exported == set(_lib.SIGNATURES), sorted(exported ^ set(_lib.SIGNATURES))
 
 
 def test_options_and_release_entry_points(monkeypatch):

@@ -10,6 +10,7 @@
 //   grads   : nlayers x 12 pointers, written (not accumulated)
 #include "common.h"
 #include "options.h"
+#include <algorithm>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -49,22 +50,27 @@ Acts carve(char* base, long T, int D, int nseq, int L, int H, int es, bool f32, 
   return a;
 }
 
+// y[M,N] = x[M,K] w[N,K]^T;  lda / ldc: row strides of x and of y (0 = dense)
 inline int linear(bool f32, const void* x, const void* w, void* y, int M, int N, int K, const void* bias, const void* resid,
-                  void* aux_out, int epi, void* ws, size_t wsb, hipStream_t s) {
+                  void* aux_out, int epi, hipStream_t s, int lda = 0, int ldc = 0) {
+  lda = lda ? lda : K;
+  ldc = ldc ? ldc : N;
+  epi |= (bias ? EPI_BIAS : 0) | (resid ? EPI_RESID : 0);
   if (f32)
-    return hmmc_gemm_f32((const float*)x, (const float*)w, (float*)y, M, N, K, K, 1, 1, K, N, 1.0f, (const float*)bias,
-                         (const float*)resid, (float*)aux_out, nullptr, epi | (bias ? EPI_BIAS : 0) | (resid ? EPI_RESID : 0), s);
-  return hmmc_gemm_f16(x, w, y, M, N, K, K, K, N, 1, 1, bias, resid, aux_out, nullptr,
-                       epi | (bias ? EPI_BIAS : 0) | (resid ? EPI_RESID : 0), nullptr, 0, s);
+    return hmmc_gemm_f32((const float*)x, (const float*)w, (float*)y, M, N, K, lda, 1, 1, K, ldc, 1.0f, (const float*)bias,
+                         (const float*)resid, (float*)aux_out, nullptr, epi, s);
+  return hmmc_gemm_f16(x, w, y, M, N, K, lda, K, ldc, 1, 1, bias, resid, aux_out, nullptr, epi, nullptr, 0, s);
 }
-// dx[M,K'] = dy[M,N'] w[N',K']
+// dx[M,K'] = dy[M,N'] w[N',K'];  ldy / ldx: row strides of dy and dx (0 = dense)
 // csum (fp16 tower only): fp32 partial column sums of dx, hmmc_gemm_f16_colsum_rows(M, K', N') rows of K' floats
 inline int dgrad(bool f32, const void* dy, const void* w, void* dx, int M, int Np, int Kp, const void* aux_in, int epi,
-                 hipStream_t s, float* csum = nullptr, size_t csum_bytes = 0) {
+                 hipStream_t s, int ldy = 0, int ldx = 0, float* csum = nullptr, size_t csum_bytes = 0) {
+  ldy = ldy ? ldy : Np;
+  ldx = ldx ? ldx : Kp;
   if (f32)
-    return hmmc_gemm_f32((const float*)dy, (const float*)w, (float*)dx, M, Kp, Np, Np, 1, Kp, 1, Kp, 1.0f, nullptr, nullptr,
+    return hmmc_gemm_f32((const float*)dy, (const float*)w, (float*)dx, M, Kp, Np, ldy, 1, Kp, 1, ldx, 1.0f, nullptr, nullptr,
                          nullptr, (const float*)aux_in, epi, s);
-  return hmmc_gemm_f16(dy, w, dx, M, Kp, Np, Np, Kp, Kp, 1, 0, nullptr, nullptr, nullptr, aux_in, epi | (csum ? EPI_COLSUM : 0),
+  return hmmc_gemm_f16(dy, w, dx, M, Kp, Np, ldy, Kp, ldx, 1, 0, nullptr, nullptr, nullptr, aux_in, epi | (csum ? EPI_COLSUM : 0),
                        csum, csum_bytes, s);
 }
 // dW[N',K'] = dy[T,N']^T x[T,K'];  ldy / ldx: row strides of dy and x (0 = dense)
@@ -97,6 +103,32 @@ inline int lead_inproj_attention(const void* ln1, const void* w_in, const void* 
   return hmmc_attention_f16_fwd_lead(qkv, att, stat, nseq, L, heads, causal, s);
 }
 
+// One layer on the unfolded kernels: x1 = xin + out_proj(attn(in_proj(ln_1(xin)))), out = x1 + c_proj(QuickGELU(c_fc(ln_2(x1)))).
+// lead (the last block of a lead_only call): everything after the attention is per-token, so out_proj, ln_2 and the MLP run
+// on the nseq leading rows only, read and written in place at stride L*D in x1 and out (ln2 / g / h are compact [nseq, .]).
+// Both forwards issue every unfolded layer through here, which keeps a class-token row bit-identical between a lead_only and
+// an all-token call.
+int layer_fwd(bool f32, const void* const* P, const Acts& a, const void* xin, void* out, long T, int nseq, int L, int heads, int D,
+              int causal, float eps, bool keep_acts, bool lead, hipStream_t s) {
+  const int dt = f32 ? 1 : 0;
+  CK(hmmc_layernorm_fwd(xin, (const float*)P[0], (const float*)P[1], a.ln1, a.m1, a.r1, nullptr, (int)T, D, D, eps, dt, s));
+  if (lead_attention(lead, f32, L)) {
+    CK(lead_inproj_attention(a.ln1, P[2], P[3], a.qkv, a.att, a.stat, T, nseq, L, heads, D, causal, s));
+  } else {
+    CK(linear(f32, a.ln1, P[2], a.qkv, (int)T, 3 * D, D, P[3], nullptr, nullptr, 0, s));
+    if (f32) CK(hmmc_temporal_attention_fwd((const float*)a.qkv, (float*)a.att, a.stat, nseq, L, heads, causal, s));
+    else CK(hmmc_attention_f16_fwd(a.qkv, a.att, a.stat, nseq, L, heads, causal, s));
+  }
+  const int R = lead ? nseq : (int)T;                 // rows of the per-token half
+  const int ldr = lead ? L * D : D;                   // their stride in the [T, D] buffers
+  // fp16 tower: the `h` slot receives QuickGELU'(pre-activation), which is all the backward needs of it
+  const int save_epi = EPI_QGELU | ((!f32 && keep_acts) ? EPI_SAVE_DGELU : 0);
+  CK(linear(f32, a.att, P[4], a.x1, R, D, D, P[5], xin, nullptr, 0, s, ldr, ldr));
+  CK(hmmc_layernorm_fwd(a.x1, (const float*)P[6], (const float*)P[7], a.ln2, a.m2, a.r2, nullptr, R, D, ldr, eps, dt, s));
+  CK(linear(f32, a.ln2, P[8], a.g, R, 4 * D, D, P[9], nullptr, keep_acts ? a.h : nullptr, save_epi, s));
+  return linear(f32, a.g, P[10], out, R, D, 4 * D, P[11], a.x1, nullptr, 0, s, 0, ldr);
+}
+
 }  // namespace
 
 extern "C" size_t hmmc_tower_act_bytes(long tokens, int D, int nseq, int L, int heads, int fp32) {
@@ -106,6 +138,15 @@ extern "C" size_t hmmc_tower_act_bytes(long tokens, int D, int nseq, int L, int 
 // nfold of these followed by (nlayers - nfold) of hmmc_tower_act_bytes(), nfold = nlayers - (last_exact ? 1 : 0)
 extern "C" size_t hmmc_tower_act_bytes_fold(long tokens, int D, int nseq, int L, int heads) {
   return carve(nullptr, tokens, D, nseq, L, heads, 2, false, true).bytes;
+}
+// layer i's slab in the acts buffer of a call: keep_acts = 0, the one slab every layer reuses; keep_acts = 1, the layout above
+// (nfold = 0: a call of hmmc_tower_fwd / hmmc_tower_bwd)
+static Acts layer_acts(const void* acts, int i, int nfold, bool keep_acts, long T, int D, int nseq, int L, int heads, bool f32) {
+  const int es = f32 ? 4 : 2;
+  if (!keep_acts) return carve((char*)acts, T, D, nseq, L, heads, es, f32);
+  const size_t slab = hmmc_tower_act_bytes(T, D, nseq, L, heads, f32), slab_f = hmmc_tower_act_bytes_fold(T, D, nseq, L, heads);
+  const size_t off = i < nfold ? (size_t)i * slab_f : (size_t)nfold * slab_f + (size_t)(i - nfold) * slab;
+  return carve((char*)acts + off, T, D, nseq, L, heads, es, f32, i < nfold);
 }
 
 // transient gradients of the backward: dh [T,4D], dqkv [T,3D], dln [T,D], dx1 [T,D], ping/pong dx [T,D] x2; the fp16 tower holds
@@ -126,7 +167,10 @@ extern "C" size_t hmmc_tower_bwd_scratch_bytes(long tokens, int D, int fp32) {
 struct PartSlot { size_t ln2, ln1, fc, attn, bytes; };
 static PartSlot part_slot(long tokens, int D, int nseq) {
   PartSlot p;
-  const size_t ln = al((size_t)hmmc_layernorm_bwd_rows((int)tokens) * 3 * D * sizeof(float));
+  // a lead-only last block runs ln_2's backward over its nseq class rows in the same slot, and the partial row count is not
+  // monotonic in the input rows
+  const int ln_rows = std::max(hmmc_layernorm_bwd_rows((int)tokens), hmmc_layernorm_bwd_rows(nseq));
+  const size_t ln = al((size_t)ln_rows * 3 * D * sizeof(float));
   p.ln2 = 0; p.ln1 = ln;
   p.fc = 2 * ln;
   p.attn = p.fc + al(hmmc_gemm_f16_colsum_rows((int)tokens, 4 * D, D) * (size_t)4 * D * sizeof(float));
@@ -145,42 +189,22 @@ static size_t group_ws_bytes(long tokens, int D) {
   return hmmc_gemm_f16_wgrad_group_workspace(Np, Kp, 4, (int)tokens);
 }
 
-static size_t general_bytes(long tokens, int D, int fp32) {
-  size_t w = hmmc_layernorm_bwd_workspace((int)tokens, D);
-  size_t c = hmmc_colsum_workspace((int)tokens, 4 * D);
-  if (c > w) w = c;
-  if (!fp32) {
-    size_t g = hmmc_gemm_f16_workspace(3 * D, D, (int)tokens);
-    size_t g2 = hmmc_gemm_f16_workspace(4 * D, D, (int)tokens);
-    size_t g3 = hmmc_gemm_f16_workspace(D, 4 * D, (int)tokens);
-    size_t g4 = hmmc_gemm_f16_workspace(D, D, (int)tokens);
-    size_t g5 = hmmc_gemm_f16_workspace(2 * D, D, (int)tokens);      // K | V rows of in_proj: a lead-only last block
-    if (g2 > g) g = g2;
-    if (g3 > g) g = g3;
-    if (g4 > g) g = g4;
-    if (g5 > g) g = g5;
-    if (g > w) w = g;
-    size_t grp = group_ws_bytes(tokens, D);          // the grouped launch takes this region when there is no second stream
-    if (grp > w) w = grp;
-  }
-  return al(w);
+// split-K slabs of the fp16 tower's weight gradients: the grouped launch, or any one of in_proj, c_fc, c_proj, out_proj and the
+// K | V rows of in_proj (a lead-only last block)
+static size_t wgrad_ws_max(long tokens, int D) {
+  const int NK[5][2] = {{3 * D, D}, {4 * D, D}, {D, 4 * D}, {D, D}, {2 * D, D}};
+  size_t w = group_ws_bytes(tokens, D);
+  for (const auto& nk : NK) w = std::max(w, hmmc_gemm_f16_workspace(nk[0], nk[1], (int)tokens));
+  return w;
 }
 
-static size_t wgrad_ws_bytes(long tokens, int D, int fp32) {
-  if (fp32) return 0;
-  const size_t grp = group_ws_bytes(tokens, D);
-  size_t g = hmmc_gemm_f16_workspace(3 * D, D, (int)tokens);
-  if (grp > g) g = grp;
-  size_t g2 = hmmc_gemm_f16_workspace(4 * D, D, (int)tokens);
-  size_t g3 = hmmc_gemm_f16_workspace(D, 4 * D, (int)tokens);
-  size_t g4 = hmmc_gemm_f16_workspace(D, D, (int)tokens);
-  size_t g5 = hmmc_gemm_f16_workspace(2 * D, D, (int)tokens);
-  if (g2 > g) g = g2;
-  if (g3 > g) g = g3;
-  if (g4 > g) g = g4;
-  if (g5 > g) g = g5;
-  return al(g);
+// the grouped launch and the weight gradients take the general region when there is no second stream
+static size_t general_bytes(long tokens, int D, int fp32) {
+  const size_t w = std::max(hmmc_layernorm_bwd_workspace((int)tokens, D), hmmc_colsum_workspace((int)tokens, 4 * D));
+  return al(fp32 ? w : std::max(w, wgrad_ws_max(tokens, D)));
 }
+
+static size_t wgrad_ws_bytes(long tokens, int D, int fp32) { return fp32 ? 0 : al(wgrad_ws_max(tokens, D)); }
 
 // [general: LayerNorm / column-sum / split-K slabs][fp16 tower backward: per-layer slots of deferred-reduction partials]
 // [split-K slabs of the weight-gradient stream]
@@ -200,46 +224,17 @@ extern "C" int hmmc_tower_fwd(const void* x, void* y, const void* const* params,
   if (!x || !y || !params || !acts || nseq <= 0 || L <= 0 || heads <= 0 || nlayers <= 0 || D != heads * 64) return HMMC_ERR_ARG;
   if (lead_only && fp32) return HMMC_ERR_UNSUPPORTED;
   const bool f32 = fp32 != 0;
-  const int es = f32 ? 4 : 2, dt = f32 ? 1 : 0;
   const long T = (long)nseq * L;
-  const size_t slab = hmmc_tower_act_bytes(T, D, nseq, L, heads, fp32);
   const void* cur = x;
   for (int i = 0; i < nlayers; ++i) {
-    const void* const* P = params + (size_t)i * 12;
-    Acts a = carve((char*)acts + (keep_acts ? (size_t)i * slab : 0), T, D, nseq, L, heads, es, f32);
-    const void* xin = cur;
-    CK(hmmc_layernorm_fwd(xin, (const float*)P[0], (const float*)P[1], a.ln1, a.m1, a.r1, nullptr, (int)T, D, D, eps, dt, s));
-    if (lead_attention(lead_only && i + 1 == nlayers, f32, L)) {
-      CK(lead_inproj_attention(a.ln1, P[2], P[3], a.qkv, a.att, a.stat, T, nseq, L, heads, D, causal, s));
-    } else {
-      CK(linear(f32, a.ln1, P[2], a.qkv, (int)T, 3 * D, D, P[3], nullptr, nullptr, 0, workspace, ws_bytes, s));
-      if (f32) CK(hmmc_temporal_attention_fwd((const float*)a.qkv, (float*)a.att, a.stat, nseq, L, heads, causal, s));
-      else CK(hmmc_attention_f16_fwd(a.qkv, a.att, a.stat, nseq, L, heads, causal, s));
-    }
+    const Acts a = layer_acts(acts, i, 0, keep_acts, T, D, nseq, L, heads, f32);
     // output of this layer: next layer's saved input slot, or y for the last layer.  Without saved activations one
     // slab is reused: the output alternates between the x and h slots (h is dead once c_proj has read g, and the
     // next layer's input is dead before its own c_fc rewrites h).
     void* out = y;
-    if (i + 1 < nlayers) out = keep_acts ? carve((char*)acts + (size_t)(i + 1) * slab, T, D, nseq, L, heads, es, f32).x
+    if (i + 1 < nlayers) out = keep_acts ? layer_acts(acts, i + 1, 0, true, T, D, nseq, L, heads, f32).x
                                          : (void*)(((i & 1) == 0) ? a.x : a.h);
-    const int save_epi = EPI_QGELU | ((!f32 && keep_acts) ? EPI_SAVE_DGELU : 0);
-    if (lead_only && i + 1 == nlayers) {
-      // leading rows only: x1 and y are addressed in place (row n*L of the [T, D] buffers), ln2 / g / h are compact [nseq, .]
-      const int ldl = L * D;
-      CK(hmmc_gemm_f16(a.att, P[4], a.x1, nseq, D, D, ldl, D, ldl, 1, 1, P[5], xin, nullptr, nullptr, EPI_BIAS | EPI_RESID,
-                       nullptr, 0, s));
-      CK(hmmc_layernorm_fwd(a.x1, (const float*)P[6], (const float*)P[7], a.ln2, a.m2, a.r2, nullptr, nseq, D, ldl, eps, dt, s));
-      CK(linear(f32, a.ln2, P[8], a.g, nseq, 4 * D, D, P[9], nullptr, keep_acts ? a.h : nullptr, save_epi, workspace, ws_bytes, s));
-      CK(hmmc_gemm_f16(a.g, P[10], out, nseq, D, 4 * D, 4 * D, 4 * D, ldl, 1, 1, P[11], a.x1, nullptr, nullptr,
-                       EPI_BIAS | EPI_RESID, nullptr, 0, s));
-      cur = out;
-      continue;
-    }
-    CK(linear(f32, a.att, P[4], a.x1, (int)T, D, D, P[5], xin, nullptr, 0, workspace, ws_bytes, s));
-    CK(hmmc_layernorm_fwd(a.x1, (const float*)P[6], (const float*)P[7], a.ln2, a.m2, a.r2, nullptr, (int)T, D, D, eps, dt, s));
-    // fp16 tower: the `h` slot receives QuickGELU'(pre-activation), which is all the backward needs of it
-    CK(linear(f32, a.ln2, P[8], a.g, (int)T, 4 * D, D, P[9], nullptr, keep_acts ? a.h : nullptr, save_epi, workspace, ws_bytes, s));
-    CK(linear(f32, a.g, P[10], out, (int)T, D, 4 * D, P[11], a.x1, nullptr, 0, workspace, ws_bytes, s));
+    CK(layer_fwd(f32, params + (size_t)i * 12, a, cur, out, T, nseq, L, heads, D, causal, eps, keep_acts, lead_only && i + 1 == nlayers, s));
     cur = out;
   }
   return HMMC_OK;
@@ -302,13 +297,7 @@ extern "C" int hmmc_tower_fwd_fused(const void* x, const float* x_stat, void* y,
   std::vector<FoldLayer> fl(nlayers);
   const FoldWs fw = fold_carve((char*)fold_ws, T, D, nlayers, keep_acts, fl.data());
   if (fold_bytes < fw.bytes) return HMMC_ERR_WORKSPACE;
-  const size_t slab = hmmc_tower_act_bytes(T, D, nseq, L, heads, 0), slab_f = hmmc_tower_act_bytes_fold(T, D, nseq, L, heads);
-  // layer i's saved activations (training): folded layers first, in the compact slab
-  auto acts_of = [&](int i) {
-    if (!keep_acts) return carve((char*)acts, T, D, nseq, L, heads, 2, false);
-    const size_t off = i < nfold ? (size_t)i * slab_f : (size_t)nfold * slab_f + (size_t)(i - nfold) * slab;
-    return carve((char*)acts + off, T, D, nseq, L, heads, 2, false, i < nfold);
-  };
+  auto acts_of = [&](int i) { return layer_acts(acts, i, nfold, keep_acts, T, D, nseq, L, heads, false); };
   // folded weights and column terms of every folded layer (16 layers = 32 matrices per launch)
   for (int l0 = 0; l0 < nfold; l0 += 16) {
     const void* W[32]; const float* gm[32]; const float* bt[32]; const void* bs[32]; void* Wf[32]; float* cd[32]; int N[32];
@@ -330,23 +319,8 @@ extern "C" int hmmc_tower_fwd_fused(const void* x, const float* x_stat, void* y,
     if (i + 1 < nlayers) out = keep_acts ? (void*)acts_of(i + 1).x : (void*)(((i & 1) == 0) ? a.x : a.h);
     const bool lead = lead_only && i + 1 == nlayers;
     const int ldl = L * D;
-    if (i >= nfold) {
-      // the last layer on the unfolded kernels (as hmmc_tower_fwd)
-      const int save_epi = EPI_QGELU | (keep_acts ? EPI_SAVE_DGELU : 0);
-      const int R = lead ? nseq : (int)T;                 // rows of the per-token half
-      const int ldr = lead ? ldl : D;                     // their stride in the [T, D] buffers
-      CK(hmmc_layernorm_fwd(xin, (const float*)P[0], (const float*)P[1], a.ln1, a.m1, a.r1, nullptr, (int)T, D, D, eps, 0, s));
-      if (lead_attention(lead, false, L)) {
-        CK(lead_inproj_attention(a.ln1, P[2], P[3], a.qkv, a.att, a.stat, T, nseq, L, heads, D, causal, s));
-      } else {
-        CK(hmmc_gemm_f16(a.ln1, P[2], a.qkv, (int)T, 3 * D, D, D, D, 3 * D, 1, 1, P[3], nullptr, nullptr, nullptr, EPI_BIAS, nullptr, 0, s));
-        CK(hmmc_attention_f16_fwd(a.qkv, a.att, a.stat, nseq, L, heads, causal, s));
-      }
-      CK(hmmc_gemm_f16(a.att, P[4], a.x1, R, D, D, ldr, D, ldr, 1, 1, P[5], xin, nullptr, nullptr, EPI_BIAS | EPI_RESID, nullptr, 0, s));
-      CK(hmmc_layernorm_fwd(a.x1, (const float*)P[6], (const float*)P[7], a.ln2, a.m2, a.r2, nullptr, R, D, ldr, eps, 0, s));
-      CK(hmmc_gemm_f16(a.ln2, P[8], a.g, R, 4 * D, D, D, D, 4 * D, 1, 1, P[9], nullptr, keep_acts ? a.h : nullptr, nullptr,
-                       EPI_BIAS | save_epi, nullptr, 0, s));
-      CK(hmmc_gemm_f16(a.g, P[10], out, R, D, 4 * D, 4 * D, 4 * D, ldr, 1, 1, P[11], a.x1, nullptr, nullptr, EPI_BIAS | EPI_RESID, nullptr, 0, s));
+    if (i >= nfold) {                                     // the last layer on the unfolded kernels
+      CK(layer_fwd(false, P, a, xin, out, T, nseq, L, heads, D, causal, eps, keep_acts, lead, s));
       cur = out;
       continue;
     }
@@ -386,28 +360,22 @@ extern "C" int hmmc_tower_fwd_fused(const void* x, const float* x_stat, void* y,
                             nullptr, 0, s));
       CK(hmmc_attention_f16_fwd_lead(a.qkv, a.att, a.stat, nseq, L, heads, causal, s));
     }
+    // the per-token half; lead: on the leading rows only, as layer_fwd (so a class-token row comes out bit-identical to the
+    // all-token pass)
+    const int R = lead ? nseq : (int)T, ldr = lead ? ldl : D;
     const int fc_epi = EPI_LNFOLD | EPI_QGELU | (keep_acts ? EPI_SAVE_DGELU : 0);
     void* const fc_aux = keep_acts ? a.h : nullptr;
-    if (lead) {
-      // the last block's per-token half on the leading rows only, as hmmc_tower_fwd: the same folded arithmetic on rows
-      // addressed in place at stride L*D (so a class-token row comes out bit-identical to the all-token pass)
-      CK(hmmc_gemm_f16_fold(a.att, P[4], a.x1, nseq, D, D, ldl, D, ldl, 1, P[5], xin, nullptr, nullptr, EPI_BIAS | EPI_RESID | EPI_ROWSTAT, nullptr,
-                            nullptr, fw.part, nullptr, 0, s));
-      CK(hmmc_rowstat_finalize(fw.part, stat2, nparts, nseq, D, eps, s));
-      CK(hmmc_gemm_f16_fold(a.x1, fl[i].w2, a.g, nseq, 4 * D, D, ldl, D, 4 * D, 1, nullptr, nullptr, fc_aux, nullptr, fc_epi, stat2, fl[i].cd2, nullptr,
-                            nullptr, 0, s));
-      CK(hmmc_gemm_f16(a.g, P[10], out, nseq, D, 4 * D, 4 * D, 4 * D, ldl, 1, 1, P[11], a.x1, nullptr, nullptr, EPI_BIAS | EPI_RESID, nullptr, 0, s));
-      cur = out;
-      continue;
-    }
-    CK(hmmc_gemm_f16_fold(a.att, P[4], a.x1, (int)T, D, D, D, D, D, 1, P[5], xin, nullptr, nullptr, EPI_BIAS | EPI_RESID | EPI_ROWSTAT, nullptr, nullptr,
+    CK(hmmc_gemm_f16_fold(a.att, P[4], a.x1, R, D, D, ldr, D, ldr, 1, P[5], xin, nullptr, nullptr, EPI_BIAS | EPI_RESID | EPI_ROWSTAT, nullptr, nullptr,
                           fw.part, nullptr, 0, s));
-    CK(hmmc_rowstat_finalize(fw.part, stat2, nparts, (int)T, D, eps, s));
-    CK(hmmc_gemm_f16_fold(a.x1, fl[i].w2, a.g, (int)T, 4 * D, D, D, D, 4 * D, 1, nullptr, nullptr, fc_aux, nullptr, fc_epi, stat2, fl[i].cd2, nullptr,
+    CK(hmmc_rowstat_finalize(fw.part, stat2, nparts, R, D, eps, s));
+    CK(hmmc_gemm_f16_fold(a.x1, fl[i].w2, a.g, R, 4 * D, D, ldr, D, 4 * D, 1, nullptr, nullptr, fc_aux, nullptr, fc_epi, stat2, fl[i].cd2, nullptr,
                           nullptr, 0, s));
     const bool more = i + 1 < nfold;                      // the next layer is folded too: it needs the row pairs of this output
-    CK(hmmc_gemm_f16_fold(a.g, P[10], out, (int)T, D, 4 * D, 4 * D, 4 * D, D, 1, P[11], a.x1, nullptr, nullptr,
-                          EPI_BIAS | EPI_RESID | (more ? EPI_ROWSTAT : 0), nullptr, nullptr, more ? fw.part : nullptr, nullptr, 0, s));
+    if (lead)
+      CK(hmmc_gemm_f16(a.g, P[10], out, nseq, D, 4 * D, 4 * D, 4 * D, ldl, 1, 1, P[11], a.x1, nullptr, nullptr, EPI_BIAS | EPI_RESID, nullptr, 0, s));
+    else
+      CK(hmmc_gemm_f16_fold(a.g, P[10], out, (int)T, D, 4 * D, 4 * D, 4 * D, D, 1, P[11], a.x1, nullptr, nullptr,
+                            EPI_BIAS | EPI_RESID | (more ? EPI_ROWSTAT : 0), nullptr, nullptr, more ? fw.part : nullptr, nullptr, 0, s));
     if (more) {
       float* const next = keep_acts ? acts_of(i + 1).m1 : fw.stat;
       CK(hmmc_rowstat_finalize(fw.part, next, nparts, (int)T, D, eps, s));
@@ -543,7 +511,6 @@ static int tower_bwd_impl(const void* dy, void* dx, const void* x0, const void* 
   const bool f32 = fp32 != 0;
   const int es = f32 ? 4 : 2, dt = f32 ? 1 : 0;
   const long T = (long)nseq * L;
-  const size_t slab = hmmc_tower_act_bytes(T, D, nseq, L, heads, fp32);
   char* sp = (char*)scratch;
   void* dh_set[2]; void* dqkv_set[2]; void* dx1_set[2];
   const bool sets2 = two_sets(T, D, fp32);
@@ -615,21 +582,22 @@ static int tower_bwd_impl(const void* dy, void* dx, const void* x0, const void* 
     if (two && done_set[k] && hipStreamWaitEvent(s, syncp->done[k], 0) != hipSuccess) return HMMC_ERR_LAUNCH;
     return 0;
   };
+  // `s` waits for the grouped launch that read operand set k: the chain is about to overwrite it
+  auto wait_group = [&](int k) -> int {
+    if (two && gdone_set[k]) {
+      if (hipStreamWaitEvent(s, syncp->gdone[k], 0) != hipSuccess) return HMMC_ERR_LAUNCH;
+      gdone_set[k] = false;
+    }
+    return 0;
+  };
   const void* g_in = dy;
   const int ldl = L * D;                         // lead_only: row stride between the leading tokens of consecutive sequences
-  if (lead_only) CK(hmmc_colsum(dy, grads[(size_t)(nlayers - 1) * 12 + 11], nseq, D, ldl, dt, dt, 0, workspace, gen, s));
-  else CK(hmmc_colsum(dy, grads[(size_t)(nlayers - 1) * 12 + 11], (int)T, D, D, dt, dt, 0, workspace, gen, s));
+  CK(hmmc_colsum(dy, grads[(size_t)(nlayers - 1) * 12 + 11], lead_only ? nseq : (int)T, D, lead_only ? ldl : D, dt, dt, 0, workspace,
+                 gen, s));
   for (int i = nlayers - 1; i >= 0; --i) {
     const void* const* P = params + (size_t)i * 12;
     void* const* G = grads + (size_t)i * 12;
-    Acts a;
-    if (fb) {
-      const size_t slab_f = hmmc_tower_act_bytes_fold(T, D, nseq, L, heads);
-      const size_t off = i < fb->nfold ? (size_t)i * slab_f : (size_t)fb->nfold * slab_f + (size_t)(i - fb->nfold) * slab;
-      a = carve((char*)acts + off, T, D, nseq, L, heads, es, f32, i < fb->nfold);
-    } else {
-      a = carve((char*)acts + (size_t)i * slab, T, D, nseq, L, heads, es, f32);
-    }
+    const Acts a = layer_acts(acts, i, fb ? fb->nfold : 0, true, T, D, nseq, L, heads, f32);
     const void* xin = i == 0 ? x0 : (const void*)a.x;
     void* g_out = i == 0 ? dx : ping[i & 1];
     char* const sl = part_base + (size_t)i * slot.bytes;           // this layer's slot of partial matrices (fp16 tower)
@@ -637,162 +605,98 @@ static int tower_bwd_impl(const void* dy, void* dx, const void* x0, const void* 
     float* const p_ln1 = (float*)(sl + slot.ln1);
     float* const p_fc = (float*)(sl + slot.fc);
     float* const p_attn = (float*)(sl + slot.attn);
-    const size_t fc_bytes = slot.attn - slot.fc, attn_bytes = slot.bytes - slot.attn;
     // this layer's set of transient gradients; a set is written again two layers on, after the grouped launch that read it
     const int par = i & 1;
     void* const dh = dh_set[par];
     void* const dqkv = dqkv_set[par];
     void* const dx1 = dx1_set[par];
-    const bool group_layer = grouped && !(lead_only && i + 1 == nlayers);
-    if (two && gdone_set[par]) {
-      if (hipStreamWaitEvent(s, syncp->gdone[par], 0) != hipSuccess) return HMMC_ERR_LAUNCH;
-      gdone_set[par] = false;
-    }
-    if (fb && i < fb->nfold) {
-      // ---- a layer hmmc_tower_fwd_fused ran folded (never a lead-only one: hmmc_tower_bwd_fold checks)
-      const FoldLayer& f = fb->fl[i];
-      const float* const stat1 = a.m1;            // row pairs of the layer's input x
-      const float* const stat2 = a.m2;            // ... and of x1
-      CK(before_overwrite(1));
-      {
-        // dh~ = rstd2_r x [(g_in W_proj) o QuickGELU'(h)], bias partials of the unscaled product
-        const int rows = (int)hmmc_gemm_f16_colsum_rows((int)T, 4 * D, D);
-        CK(hmmc_gemm_f16_fold(g_in, P[10], dh, (int)T, 4 * D, D, D, 4 * D, 4 * D, 0, nullptr, nullptr, nullptr, a.h,
-                              EPI_MULAUX | EPI_COLSUM | EPI_ROWSCALE, stat2, nullptr, nullptr, p_fc, fc_bytes, s));
-        defer(p_fc, rows, 4 * D, 4 * D, G[9], dt);
-      }
-      CK(hmmc_gemm_f16(dh, f.w2, dln, (int)T, D, 4 * D, 4 * D, D, D, 1, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, s));    // du~2
-      CK(before_overwrite(2));
-      CK(ln_bwd_folded(dln, a.x1, stat2, g_in, dx1, G[5], (int)T, D, p_ln2));                   // G[5]: out_proj bias = colsum(dx1)
-      CK(dgrad(f32, dx1, P[4], dln, (int)T, D, D, nullptr, 0, s));                             // datt
-      CK(before_overwrite(3));
-      CK(hmmc_attention_f16_bwd_scaled(a.qkv, a.att, a.stat, dln, dqkv, p_attn, stat1, nseq, L, heads, causal, s));       // rstd1_r x dqkv
-      defer(p_attn, nseq, 3 * D, 3 * D, G[3], dt);
-      {
-        const void* gy[4] = {g_in, dh, dx1, dqkv};
-        const void* gx[4] = {a.g, a.x1, a.att, xin};
-        void* gw[4] = {G[10], nullptr, G[4], nullptr};
-        float* gw32[4] = {nullptr, f.s2, nullptr, f.s1};
-        int Np[4], Kp[4];
-        group_dims(D, Np, Kp);
-        if (two && (hipEventRecord(syncp->ready, s) != hipSuccess || hipStreamWaitEvent(sw, syncp->ready, 0) != hipSuccess)) return HMMC_ERR_LAUNCH;
-        CK(hmmc_gemm_f16_wgrad_group(gy, gx, gw, gw32, Np, Kp, 4, (int)T, two ? wws : workspace, two ? wws_bytes : gen, sw));
-        if (two) {
-          if (hipEventRecord(syncp->gdone[par], sw) != hipSuccess) return HMMC_ERR_LAUNCH;
-          gdone_set[par] = true;
-        }
-      }
-      CK(hmmc_gemm_f16(dqkv, f.w1, dln, (int)T, D, 3 * D, 3 * D, D, D, 1, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, s));   // du~1
-      CK(before_overwrite(0));
-      if (two && gdone_set[par ^ 1]) {
-        if (hipStreamWaitEvent(s, syncp->gdone[par ^ 1], 0) != hipSuccess) return HMMC_ERR_LAUNCH;
-        gdone_set[par ^ 1] = false;
-      }
-      CK(ln_bwd_folded(dln, xin, stat1, dx1, g_out, i > 0 ? grads[(size_t)(i - 1) * 12 + 11] : nullptr, (int)T, D, p_ln1));
-      g_in = g_out;
-      continue;
-    }
-    if (lead_only && i + 1 == nlayers) {
-      // Last block, leading rows only (see hmmc_tower_fwd): g_in = dy and x1 / att are addressed at stride L*D, dh / dln / ln2 /
-      // g / h are compact [nseq, .].  dx1 and the attention-output gradient are full [T, D] buffers that the attention and
-      // ln_1 backward read whole: zero everywhere except the leading rows.
-      if (hipMemsetAsync(dx1, 0, (size_t)T * D * es, s) != hipSuccess) return HMMC_ERR_LAUNCH;
-      CK(side_wgrad(0, g_in, a.g, G[10], D, 4 * D, nseq, ldl, 0));
-      const int rows = (int)hmmc_gemm_f16_colsum_rows(nseq, 4 * D, D);
-      CK(hmmc_gemm_f16(g_in, P[10], dh, nseq, 4 * D, D, ldl, 4 * D, 4 * D, 1, 0, nullptr, nullptr, nullptr, a.h,
-                       EPI_MULAUX | EPI_COLSUM, p_fc, fc_bytes, s));
-      defer(p_fc, rows, 4 * D, 4 * D, G[9], dt);
-      CK(side_wgrad(1, dh, a.ln2, G[8], 4 * D, D, nseq));
-      CK(dgrad(f32, dh, P[8], dln, nseq, 4 * D, D, nullptr, 0, s));
-      CK(ln_bwd(dln, a.x1, (const float*)P[6], a.m2, a.r2, g_in, dx1, (float*)G[6], (float*)G[7], G[5], nseq, ldl,
-                p_ln2));                                                       // G[5]: out_proj bias = colsum(dx1 rows)
-      CK(side_wgrad(2, dx1, a.att, G[4], D, D, nseq, ldl, ldl));
-      if (lead_attention(true, f32, L)) {
-        // The forward ran this block's attention for query 0 only (lead_inproj_attention).  datt exists on the class rows alone
-        // (the rest of dln is not initialised and not read); the attention backward writes dK | dV of every token and dQ of the
-        // class tokens; no gradient reaches the other tokens' Q, so the in_proj weight gradient is (dK | dV)^T ln1 over every
-        // token plus dQ^T ln1 over the class rows, and the data gradient is (dK | dV) W_kv with the class rows recomputed over
-        // the whole of K = 3D (one rounding, as in the all-token pass).
-        CK(hmmc_gemm_f16(dx1, P[4], dln, nseq, D, D, ldl, D, ldl, 1, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, s));
-        CK(before_overwrite(3));
-        CK(hmmc_attention_f16_bwd_lead(a.qkv, a.att, a.stat, dln, dqkv, p_attn, nullptr, nseq, L, heads, causal, s));
-        defer(p_attn, nseq, 3 * D, 3 * D, G[3], dt);
-        half_t* const dqkv_h = (half_t*)dqkv;
-        half_t* const gw = (half_t*)G[2];
-        const half_t* const w_in = (const half_t*)P[2];
-        CK(side_wgrad(3, dqkv_h + D, a.ln1, gw + (size_t)D * D, 2 * D, D, (int)T, 3 * D, 0));
-        CK(side_wgrad(3, dqkv_h, a.ln1, gw, D, D, nseq, L * 3 * D, ldl));
-        CK(hmmc_gemm_f16(dqkv_h + D, w_in + (size_t)D * D, dln, (int)T, D, 2 * D, 3 * D, D, D, 1, 0, nullptr, nullptr, nullptr, nullptr, 0,
-                         nullptr, 0, s));
-        CK(hmmc_gemm_f16(dqkv_h, w_in, dln, nseq, D, 3 * D, L * 3 * D, D, ldl, 1, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, s));
-        CK(before_overwrite(0));
-        if (two && gdone_set[par ^ 1]) {
-          if (hipStreamWaitEvent(s, syncp->gdone[par ^ 1], 0) != hipSuccess) return HMMC_ERR_LAUNCH;
-          gdone_set[par ^ 1] = false;
-        }
-        CK(ln_bwd(dln, xin, (const float*)P[0], a.m1, a.r1, dx1, g_out, (float*)G[0], (float*)G[1],
-                  i > 0 ? grads[(size_t)(i - 1) * 12 + 11] : nullptr, (int)T, D, p_ln1));
-        g_in = g_out;
-        continue;
-      }
-      if (hipMemsetAsync(dln, 0, (size_t)T * D * es, s) != hipSuccess) return HMMC_ERR_LAUNCH;
-      CK(hmmc_gemm_f16(dx1, P[4], dln, nseq, D, D, ldl, D, ldl, 1, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, s));
-    } else {
-    // MLP: x2 = x1 + c_proj(QuickGELU(c_fc(ln2)))
-    if (!group_layer) CK(side_wgrad(0, g_in, a.g, G[10], D, 4 * D));
+    // folded: a layer hmmc_tower_fwd_fused ran folded (never a lead-only one: hmmc_tower_bwd_fold checks); its row pairs of x
+    // and x1 are in the m1 / m2 slots.  The weight gradients of a folded layer always go in the grouped launch.
+    const FoldLayer* const f = fb && i < fb->nfold ? &fb->fl[i] : nullptr;
+    // lead: the last block of a lead_only call (see hmmc_tower_fwd).  Its per-token half runs on the R = nseq leading rows: g_in = dy
+    // and x1 / att are addressed at stride L*D, dh / dln / ln2 / g / h are compact [nseq, .].  dx1 and the attention-output
+    // gradient are full [T, D] buffers that the attention and ln_1 backward read whole: zero everywhere except the leading rows.
+    const bool lead = lead_only && i + 1 == nlayers;
+    const int R = lead ? nseq : (int)T, ldr = lead ? ldl : D;
+    const bool group_layer = grouped && !lead;
+    CK(wait_group(par));
+    // ---- MLP, x2 = x1 + c_proj(QuickGELU(c_fc(ln2))): dh, dx1 and datt (in dln)
+    if (lead && hipMemsetAsync(dx1, 0, (size_t)T * D * es, s) != hipSuccess) return HMMC_ERR_LAUNCH;
+    if (!group_layer) CK(side_wgrad(0, g_in, a.g, G[10], D, 4 * D, R, ldr, 0));
     CK(before_overwrite(1));
     if (f32) {
       CK(dgrad(f32, g_in, P[10], dh, (int)T, D, 4 * D, a.h, EPI_DGELU, s));
       CK(hmmc_colsum(dh, G[9], (int)T, 4 * D, 4 * D, dt, dt, 0, workspace, gen, s));
     } else {
-      const int rows = (int)hmmc_gemm_f16_colsum_rows((int)T, 4 * D, D);
-      CK(dgrad(f32, g_in, P[10], dh, (int)T, D, 4 * D, a.h, EPI_MULAUX, s, p_fc, fc_bytes));
-      defer(p_fc, rows, 4 * D, 4 * D, G[9], dt);
+      const size_t fc_bytes = slot.attn - slot.fc;
+      if (f)        // dh~ = rstd2_r x [(g_in W_proj) o QuickGELU'(h)], bias partials of the unscaled product
+        CK(hmmc_gemm_f16_fold(g_in, P[10], dh, (int)T, 4 * D, D, D, 4 * D, 4 * D, 0, nullptr, nullptr, nullptr, a.h,
+                              EPI_MULAUX | EPI_COLSUM | EPI_ROWSCALE, a.m2, nullptr, nullptr, p_fc, fc_bytes, s));
+      else
+        CK(dgrad(f32, g_in, P[10], dh, R, D, 4 * D, a.h, EPI_MULAUX, s, ldr, 0, p_fc, fc_bytes));
+      defer(p_fc, (int)hmmc_gemm_f16_colsum_rows(R, 4 * D, D), 4 * D, 4 * D, G[9], dt);
     }
-    if (!group_layer) CK(side_wgrad(1, dh, a.ln2, G[8], 4 * D, D));
-    CK(dgrad(f32, dh, P[8], dln, (int)T, 4 * D, D, nullptr, 0, s));
+    if (!group_layer) CK(side_wgrad(1, dh, a.ln2, G[8], 4 * D, D, R));
+    CK(dgrad(f32, dh, f ? f->w2 : P[8], dln, R, 4 * D, D, nullptr, 0, s));              // folded: du~2
     CK(before_overwrite(2));
-    CK(ln_bwd(dln, a.x1, (const float*)P[6], a.m2, a.r2, g_in, dx1, (float*)G[6], (float*)G[7], G[5], (int)T, D,
-              p_ln2));                                                         // G[5]: out_proj bias = colsum(dx1)
-    // attention: x1 = x + out_proj(attn(in_proj(ln1)))
-    if (!group_layer) CK(side_wgrad(2, dx1, a.att, G[4], D, D));
-    CK(dgrad(f32, dx1, P[4], dln, (int)T, D, D, nullptr, 0, s));                 // datt (reuses dln)
-    }
+    if (f) CK(ln_bwd_folded(dln, a.x1, a.m2, g_in, dx1, G[5], (int)T, D, p_ln2));     // G[5]: out_proj bias = colsum(dx1)
+    else CK(ln_bwd(dln, a.x1, (const float*)P[6], a.m2, a.r2, g_in, dx1, (float*)G[6], (float*)G[7], G[5], R, ldr, p_ln2));
+    if (!group_layer) CK(side_wgrad(2, dx1, a.att, G[4], D, D, R, ldr, ldr));
+    // the attention of a lead_attention() block reads datt on the leading rows alone
+    const bool lead_attn = lead_attention(lead, f32, L);
+    if (lead && !lead_attn && hipMemsetAsync(dln, 0, (size_t)T * D * es, s) != hipSuccess) return HMMC_ERR_LAUNCH;
+    CK(dgrad(f32, dx1, P[4], dln, R, D, D, nullptr, 0, s, ldr, ldr));                    // datt
+    // ---- attention, x1 = x + out_proj(attn(in_proj(ln1))): dqkv, the layer's remaining weight gradients and dln = d(ln1)
     CK(before_overwrite(3));
     if (f32) {
       CK(hmmc_temporal_attention_bwd((const float*)a.qkv, a.stat, (const float*)dln, (float*)dqkv, nseq, L, heads, s));
       CK(hmmc_colsum(dqkv, G[3], (int)T, 3 * D, 3 * D, dt, dt, 0, workspace, gen, s));
     } else {
-      CK(hmmc_attention_f16_bwd(a.qkv, a.att, a.stat, dln, dqkv, p_attn, nseq, L, heads, causal, s));
+      if (f) CK(hmmc_attention_f16_bwd_scaled(a.qkv, a.att, a.stat, dln, dqkv, p_attn, a.m1, nseq, L, heads, causal, s));   // rstd1_r x dqkv
+      else if (lead_attn) CK(hmmc_attention_f16_bwd_lead(a.qkv, a.att, a.stat, dln, dqkv, p_attn, nullptr, nseq, L, heads, causal, s));
+      else CK(hmmc_attention_f16_bwd(a.qkv, a.att, a.stat, dln, dqkv, p_attn, nseq, L, heads, causal, s));
       defer(p_attn, nseq, 3 * D, 3 * D, G[3], dt);
-      (void)attn_bytes;
     }
-    if (group_layer) {
-      // all four weight gradients of the layer, now that the last operand (dqkv) exists
-      const void* gy[4] = {g_in, dh, dx1, dqkv};
-      const void* gx[4] = {a.g, a.ln2, a.att, a.ln1};
-      void* gw[4] = {G[10], G[8], G[4], G[2]};
-      int Np[4], Kp[4];
-      group_dims(D, Np, Kp);
-      if (two && (hipEventRecord(syncp->ready, s) != hipSuccess || hipStreamWaitEvent(sw, syncp->ready, 0) != hipSuccess)) return HMMC_ERR_LAUNCH;
-      CK(hmmc_gemm_f16_wgrad_group(gy, gx, gw, nullptr, Np, Kp, 4, (int)T, two ? wws : workspace, two ? wws_bytes : gen, sw));
-      if (two) {
-        if (hipEventRecord(syncp->gdone[par], sw) != hipSuccess) return HMMC_ERR_LAUNCH;
-        gdone_set[par] = true;
-      }
+    if (lead_attn) {
+      // The forward ran this block's attention for query 0 only (lead_inproj_attention); the attention backward wrote dK | dV
+      // of every token and dQ of the class tokens.  No gradient reaches the other tokens' Q, so the in_proj weight gradient is
+      // (dK | dV)^T ln1 over every token plus dQ^T ln1 over the class rows, and the data gradient is (dK | dV) W_kv with the
+      // class rows recomputed over the whole of K = 3D (one rounding, as in the all-token pass).
+      half_t* const dqkv_h = (half_t*)dqkv;
+      half_t* const gw = (half_t*)G[2];
+      const half_t* const w_in = (const half_t*)P[2];
+      CK(side_wgrad(3, dqkv_h + D, a.ln1, gw + (size_t)D * D, 2 * D, D, (int)T, 3 * D, 0));
+      CK(side_wgrad(3, dqkv_h, a.ln1, gw, D, D, nseq, L * 3 * D, ldl));
+      CK(dgrad(f32, dqkv_h + D, w_in + (size_t)D * D, dln, (int)T, 2 * D, D, nullptr, 0, s, 3 * D, 0));
+      CK(dgrad(f32, dqkv_h, w_in, dln, nseq, 3 * D, D, nullptr, 0, s, L * 3 * D, ldl));
     } else {
-      CK(side_wgrad(3, dqkv, a.ln1, G[2], 3 * D, D));
+      if (group_layer) {
+        // all four weight gradients of the layer in one launch, now that the last operand (dqkv) exists.  A folded layer's
+        // in_proj / c_fc gradients are fp32 sums against the raw rows (x, x1) that hmmc_fold_grad_finish completes.
+        const void* gy[4] = {g_in, dh, dx1, dqkv};
+        const void* gx[4] = {a.g, f ? a.x1 : a.ln2, a.att, f ? xin : a.ln1};
+        void* gw[4] = {G[10], f ? nullptr : G[8], G[4], f ? nullptr : G[2]};
+        float* gw32[4] = {nullptr, f ? f->s2 : nullptr, nullptr, f ? f->s1 : nullptr};
+        int Np[4], Kp[4];
+        group_dims(D, Np, Kp);
+        if (two && (hipEventRecord(syncp->ready, s) != hipSuccess || hipStreamWaitEvent(sw, syncp->ready, 0) != hipSuccess)) return HMMC_ERR_LAUNCH;
+        CK(hmmc_gemm_f16_wgrad_group(gy, gx, gw, f ? gw32 : nullptr, Np, Kp, 4, (int)T, two ? wws : workspace, two ? wws_bytes : gen, sw));
+        if (two) {
+          if (hipEventRecord(syncp->gdone[par], sw) != hipSuccess) return HMMC_ERR_LAUNCH;
+          gdone_set[par] = true;
+        }
+      } else {
+        CK(side_wgrad(3, dqkv, a.ln1, G[2], 3 * D, D));
+      }
+      CK(dgrad(f32, dqkv, f ? f->w1 : P[2], dln, (int)T, 3 * D, D, nullptr, 0, s));       // folded: du~1
     }
-    CK(dgrad(f32, dqkv, P[2], dln, (int)T, 3 * D, D, nullptr, 0, s));
-    // the c_proj bias gradient of the layer below is the column sum of the dx this call writes (into the buffer weight
-    // gradient 0 of the layer above read as its g_in)
+    // ---- ln_1.  Its dx goes to g_out, the buffer the layer above read as g_in (weight gradient 0 or its grouped launch); the
+    // column sum of that dx is the c_proj bias gradient of the layer below
     CK(before_overwrite(0));
-    if (two && gdone_set[par ^ 1]) {                // g_out is the g_in the grouped launch of the layer above reads
-      if (hipStreamWaitEvent(s, syncp->gdone[par ^ 1], 0) != hipSuccess) return HMMC_ERR_LAUNCH;
-      gdone_set[par ^ 1] = false;
-    }
-    CK(ln_bwd(dln, xin, (const float*)P[0], a.m1, a.r1, dx1, g_out, (float*)G[0], (float*)G[1],
-              i > 0 ? grads[(size_t)(i - 1) * 12 + 11] : nullptr, (int)T, D, p_ln1));
+    CK(wait_group(par ^ 1));
+    void* const db_below = i > 0 ? grads[(size_t)(i - 1) * 12 + 11] : nullptr;
+    if (f) CK(ln_bwd_folded(dln, xin, a.m1, dx1, g_out, db_below, (int)T, D, p_ln1));
+    else CK(ln_bwd(dln, xin, (const float*)P[0], a.m1, a.r1, dx1, g_out, (float*)G[0], (float*)G[1], db_below, (int)T, D, p_ln1));
     g_in = g_out;
   }
   if (!tasks.empty()) CK(hmmc_multi_colreduce(tasks.data(), (int)tasks.size(), s));

@@ -182,14 +182,16 @@ def test_eval_scorer_ranks_identical():
 
 
 @pytest.mark.parametrize("width,heads,L,nseq,layers,fold", [(128, 2, 10, 37, 3, False), (768, 12, 50, 96, 2, False), (768, 12, 50, 96, 3, True),
-                                                            (768, 12, 197, 16, 2, True)])
+                                                            (768, 12, 197, 16, 2, True), (768, 12, 50, 83, 2, False),
+                                                            (768, 12, 50, 83, 2, True)])
 def test_tower_lead_only_equals_full_tower(width, heads, L, nseq, layers, fold, monkeypatch):
     """hmmc_tower_fwd/bwd with lead_only run the last block's per-token half - and, for sequences of at most 64 tokens, its
     Q projection and attention (round 4) - on the class-token rows alone: those rows of the output must EQUAL the full
     computation's, the input gradient and every parameter gradient agree with it (no gradient reaches the skipped rows; weight
     gradients differ only in the order of their fp32 partial sums).  fold: the training path of the frame tower
     (hmmc_tower_fwd_fused(keep_acts) + hmmc_tower_bwd_fold with the last block on the unfolded kernels); 197 tokens: the
-    long-sequence attention, which keeps the all-query path."""
+    long-sequence attention, which keeps the all-query path; 83 x 50 = 4 150 tokens: above 4 096 rows, where the LayerNorm
+    backward's partial row count for the tokens and for the nseq class rows follow different formulas."""
     from hmmc_amd import module_clip
     import hmmc_amd.functional as Fn
     torch.manual_seed(3)

@@ -77,11 +77,7 @@ __device__ __forceinline__ void lead_to_frags(half_t* tile, const u4v (&raw)[2],
 // hmmc_tower_fwd with lead_only): the SAME instruction sequence on query tile 0 with the tile's other fifteen rows as zeros - a
 // query's column of every MFMA is independent of the other columns, so row 0 of the output and its log-sum-exp are bit-identical
 // to the all-query kernel's - and only that row is stored.  The Q columns of the other tokens are never read.
-#if defined(HMMC_SCRATCH) && defined(HMMC_ATTN_FWD_WPB)
-constexpr int FWD_WPB = HMMC_ATTN_FWD_WPB;      // scratch experiments: waves per workgroup of the forward
-#else
 constexpr int FWD_WPB = 4;
-#endif
 template <int KT, bool LEAD = false>
 __global__ __launch_bounds__(64 * FWD_WPB, 3) void attn_fwd_kernel(AttnArgs p) {
   constexpr int LP = 16 * KT;
@@ -195,10 +191,10 @@ __global__ __launch_bounds__(64 * FWD_WPB, 3) void attn_fwd_kernel(AttnArgs p) {
 //    first pair of query tiles; dK and dV are written for every token, dQ for query 0 only - the Q columns of the other rows
 //    of dqkv are NOT written (their gradient is exactly zero; the tower's data and weight gradients do not read them).
 // Workgroups of TWO waves (round 5; four until then): a workgroup's LDS and wave slots come free when its last wave ends, so
-// smaller groups refill a CU's eight slots sooner (scratch/attn_abl.sh, 3 072 x 50 x 12: 430 us with 4 waves per workgroup, 415 with
-// 2, 412 with 1, 468 with 8).  The same ablations say where the time goes: 232 us with the arithmetic removed (loads, fragment
+// smaller groups refill a CU's eight slots sooner (3 072 x 50 x 12: 430 us with 4 waves per workgroup, 415 with
+// 2, 412 with 1, 468 with 8).  Ablation builds say where the time goes: 232 us with the arithmetic removed (loads, fragment
 // shuffles and stores only), -82 / -100 us with the dV / dK pass of phase 2 removed - load time and compute time ADD.  A
-// persistent, software-pipelined form (next pair's operands by LDS-DMA under the current pair's phases; scratch/attn_bwd_pipe.patch,
+// persistent, software-pipelined form (next pair's operands by LDS-DMA under the current pair's phases;
 // bit-identical on its first run) needs 40 KiB of LDS per wave = one wave per SIMD, and one wave's dependent MFMA / exp / LDS
 // chain takes 16.5 us per pair alone (594 us); two waves per SIMD sharing the pipes are what hides it here (23 us per pair and wave).
 constexpr int BWD_WPB = 2;
@@ -326,9 +322,6 @@ __global__ __launch_bounds__(64 * BWD_WPB, 2) void attn_bwd_kernel(AttnArgs p) {
   // memory and reloaded behind full vmcnt waits in the middle of the MFMA stream.
 #pragma unroll
   for (int pass = 0; pass < 2; ++pass) {
-#if defined(HMMC_SCRATCH) && defined(HMMC_ATTN_ABL)
-    if (pass == HMMC_ATTN_ABL - 1) continue;     // timing experiments only (wrong results): 1 skips the dV pass, 2 the dK pass
-#endif
     if (pass == 0) frags_to_tile<KT>(xt, df, lane); else frags_to_tile<KT>(xt, qf, lane);
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) csum[dt] = f4{0.f, 0.f, 0.f, 0.f};

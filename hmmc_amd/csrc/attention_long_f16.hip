@@ -294,16 +294,7 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void attn_long_bwd_kernel(At
     f4 csum[4];
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) csum[dt] = f4{0.f, 0.f, 0.f, 0.f};
-#ifndef HMMC_ATTN_PIN
-#define HMMC_ATTN_PIN 1
-#endif
-#ifndef HMMC_ATTN_SKIP
-#define HMMC_ATTN_SKIP 0          // timing / register experiments (scratch/): 1 skips phase 1, 2 skips phase 2 (wrong results)
-#endif
-#if HMMC_ATTN_SKIP != 0 && !defined(HMMC_SCRATCH)
-#error "HMMC_ATTN_SKIP builds compute wrong results: scratch experiments only (-DHMMC_SCRATCH)"
-#endif
-    for (int qt = wid; qt < ntq && HMMC_ATTN_SKIP != 1; qt += NW) {
+    for (int qt = wid; qt < ntq; qt += NW) {
       const int q0 = qt * 16, qi = q0 + c;
       const u4v z = {0u, 0u, 0u, 0u};
       if constexpr (LEAD) {                      // rows 1..15 of the tile as zeros (every lane loaded row 0)
@@ -430,7 +421,7 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void attn_long_bwd_kernel(At
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2) {
       const int kt = wid + s2 * NW;
-      if (kt >= nt || HMMC_ATTN_SKIP == 2) break;
+      if (kt >= nt) break;
       const int key = kt * 16 + c;
       const bool key_ok = key < L;
       const h8 (&kf)[2] = kfr[s2];
@@ -479,9 +470,7 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void attn_long_bwd_kernel(At
           av[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(dT[dt], cat4(p16[0], p16[1]), av[dt], 0, 0, 0);
           ak[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(qT[dt], cat4(ds16[0], ds16[1]), ak[dt], 0, 0, 0);
         }
-#if HMMC_ATTN_PIN
         __builtin_amdgcn_sched_barrier(0);           // keep the scheduler from hoisting the next pairs' 28 fragment reads over this one
-#endif
       }
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) ak[dt] *= 0.125f;

@@ -24,22 +24,6 @@
 // flight across the compute of tile t (counted vmcnt + raw s_barrier).
 #include "common.h"
 #include "options.h"
-#include <cstdlib>
-
-#ifndef HMMC_DBG
-#define HMMC_DBG 0   // diagnostics (scratch/): 1 no global stores, 2 no epilogue (wrong results; timing only);
-                     // 3 / 4 / 5: s_memrealtime stamps of the third work item into p.ws (scratch/gemm_stamps.py), 4 = 1 + stamps, 5 = 2 + stamps
-#endif
-
-#ifndef HMMC_PHASES
-#define HMMC_PHASES 2  // segments of the 256x256 K-loop per K-tile and group: 2 x 32 MFMAs (product); 4 x 16 MFMAs = rounds 1-2 (scratch)
-#endif
-#ifndef HMMC_PF
-#define HMMC_PF 6     // prefetch distance of the 256x256 K-loop in half-tiles (scratch experiments build 4)
-#endif
-#if (HMMC_DBG != 0 || HMMC_PHASES != 2 || HMMC_PF != 6) && !defined(HMMC_SCRATCH)
-#error "HMMC_DBG / HMMC_PHASES / HMMC_PF other than the product values (0 / 2 / 6) are scratch experiments: build with -DHMMC_SCRATCH"
-#endif
 
 namespace {
 
@@ -302,10 +286,6 @@ __device__ __forceinline__ void epilogue_run(const GemmArgs& p, f4 (&acc)[MT][4]
   bool have_prev = false;
   auto flush = [&]() {
     if (!have_prev) return;
-#if HMMC_DBG == 1 || HMMC_DBG == 4
-    asm volatile("" :: "v"(pv0), "v"(pv1));
-    return;
-#endif
     char* sb = reinterpret_cast<char*>(pv_dst) + ((size_t)(m_base + 16 * pv_i) * p.ldc + n0) * 2u;
     if (FULL) {
       // streaming stores: a tile's output is next read by another kernel, long after the operand panels that the K loops
@@ -558,15 +538,6 @@ __device__ __forceinline__ void gemm_f16_body(const GemmArgs& p, const GemmGroup
   decode(item, split, cprob, tm, tn);
   int kt = split * p.ktps, kt_end = min(nkt, kt + p.ktps);     // host guarantees kt < kt_end for every item
   int buf = 0;
-#if HMMC_DBG >= 3
-  // 128 stamps per wave in two registers (v_writelane: stamp n lives in lane n), from the start of the wave's third item
-  unsigned st0 = 0, st1 = 0;
-  int sn = 0, items_done = 0;
-#define HMMC_STAMP() do { if (items_done >= 2 && sn < 128) { const unsigned t_ = (unsigned)__builtin_amdgcn_s_memrealtime(); \
-    st0 = (lane == sn) ? t_ : st0; st1 = (lane == sn - 64) ? t_ : st1; ++sn; } } while (0)
-#else
-#define HMMC_STAMP() do {} while (0)
-#endif
   if constexpr (MT != 8) {
     stage_tile<AK, BM, NTH>(ra, smem, wid, tid, tm * BM, kt * BKT, p.lda);
     stage_tile<BK, BN, NTH>(rb, smem + A_BYTES, wid, tid, tn * BN, kt * BKT, p.ldb);
@@ -586,10 +557,6 @@ __device__ __forceinline__ void gemm_f16_body(const GemmArgs& p, const GemmGroup
   // writes the finished tile and clears the accumulators for the next item (a zero C operand on the first K-tile
   // instead of the clear measured 1-5 % slower: it doubles the MFMA blocks of the main loop)
   auto finish_item = [&]() {
-    HMMC_STAMP();
-#if HMMC_DBG == 2 || HMMC_DBG == 5
-    _Pragma("unroll") for (int i = 0; i < MT; ++i) _Pragma("unroll") for (int j = 0; j < NT; ++j) asm volatile("" :: "v"(acc[i][j]));
-#else
     if constexpr (GRP)
       epilogue_slab<MT, NT>(p.ws + gp.pr[cprob].slab_off, gp.pr[cprob].M, gp.pr[cprob].N, acc, tm * BM + wm * (MT * 16) + (lane & 15),
                             tn * BN + wn * (NT * 16) + 4 * (lane >> 4), split);
@@ -597,15 +564,10 @@ __device__ __forceinline__ void gemm_f16_body(const GemmArgs& p, const GemmGroup
       epilogue_slab<MT, NT>(p.ws, p.M, p.N, acc, tm * BM + wm * (MT * 16) + (lane & 15), tn * BN + wn * (NT * 16) + 4 * (lane >> 4), split);
     else
       epilogue_f16<MT, EPI>(p, acc, tm * BM + wm * (MT * 16), tn * BN + wn * (NT * 16), lane, smem + 2 * STAGE_BYTES + wid * EPI_LDS_PER_WAVE);
-#endif
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
       for (int j = 0; j < NT; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
-#if HMMC_DBG >= 3
-    HMMC_STAMP();
-    ++items_done;
-#endif
   };
 
   if constexpr (MT == 8 && NT == 4) {
@@ -624,7 +586,7 @@ __device__ __forceinline__ void gemm_f16_body(const GemmArgs& p, const GemmGroup
     // both groups' segment 2 of K-tile t), and those reads retired before that barrier.
     // RAW: every half is waited for in the load segment one K-tile (four barriers) after the one that staged it, and that
     // wait precedes the barriers both groups pass before the read: a half has a whole K-tile to arrive, against half a
-    // K-tile for the last-staged half of the four-phase schedule of rounds 1-2 (-DHMMC_PHASES=4), which also paid eight
+    // K-tile for the last-staged half of the four-phase schedule of rounds 1-2, which also paid eight
     // barriers per K-tile instead of four and ran its heaviest load segment (12 reads + a half) beside only 16 MFMAs.
     // Measured on a layer's twelve GEMMs (scratch/ab_lib.sh): 6 460 -> 5 960 us; the weight gradients and the m-major data
     // gradients, whose operands stream from HBM, gain most (+12-14 %).  Past the last K-tile the DMA is still issued, out of
@@ -677,32 +639,10 @@ __device__ __forceinline__ void gemm_f16_body(const GemmArgs& p, const GemmGroup
     _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) _Pragma("unroll") for (int i = 0; i < 4; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j) \
       acc[I0 + i][J0 + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(BF[ks][j], af[ks][i], acc[I0 + i][J0 + j], 0, 0, 0); \
     __builtin_amdgcn_s_setprio(0); } while (0)
-#if HMMC_PHASES == 2
     stage_a(0); stage_b(0); stage_b(1); stage_a(1);
     s_advance();
     stage_a(0); stage_b(0); stage_b(1);
     asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // A0, B0, B1 of the first K-tile have landed
-#else
-#if HMMC_PF == 6
-#define HMMC_VMW "s_waitcnt vmcnt(8)"
-#define HMMC_ST1() stage_b(1)
-#define HMMC_ST2() do { stage_a(1); s_advance(); } while (0)
-#define HMMC_ST3() stage_a(0)
-#define HMMC_ST4() stage_b(0)
-    stage_a(0); stage_b(0); stage_b(1); stage_a(1);
-    s_advance();
-    stage_a(0); stage_b(0);
-#else      // distance 4: two half-tiles in flight at every wait (sensitivity experiment)
-#define HMMC_VMW "s_waitcnt vmcnt(4)"
-#define HMMC_ST1() stage_a(0)
-#define HMMC_ST2() stage_b(0)
-#define HMMC_ST3() stage_b(1)
-#define HMMC_ST4() do { stage_a(1); s_advance(); } while (0)
-    stage_a(0); stage_b(0); stage_b(1); stage_a(1);
-    s_advance();
-#endif
-    asm volatile(HMMC_VMW ::: "memory");
-#endif
     HMMC_BAR();
     if (wm == 1) HMMC_BAR();
     const int arow = wm * 64, brow = wn * 32;
@@ -731,7 +671,6 @@ __device__ __forceinline__ void gemm_f16_body(const GemmArgs& p, const GemmGroup
           __builtin_amdgcn_raw_ptr_buffer_load_lds(rcol, LDS_PTR(sin + 1024), 16, coff, 0, 0, 0);
         }
       }
-#if HMMC_PHASES == 2
       // segment 1
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
@@ -752,7 +691,6 @@ __device__ __forceinline__ void gemm_f16_body(const GemmArgs& p, const GemmGroup
       HMMC_MM(0, 0, b0f);
       HMMC_MM(0, 2, b1f);
       HMMC_BAR();
-      HMMC_STAMP();
       // segment 2
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
@@ -764,53 +702,6 @@ __device__ __forceinline__ void gemm_f16_body(const GemmArgs& p, const GemmGroup
       HMMC_MM(4, 2, b1f);
       HMMC_MM(4, 0, b0f);
       HMMC_BAR();
-      HMMC_STAMP();
-#else
-      // phase 1
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) b0f[ks][j] = read_frag<BK, 128>(base + 2 * HALF, brow + j * 16, ks, lane);
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) af[ks][i] = read_frag<AK, 128>(base, arow + i * 16, ks, lane);
-      HMMC_ST1();
-      asm volatile(HMMC_VMW ::: "memory");
-      HMMC_BAR();
-      HMMC_MM(0, 0, b0f);
-      HMMC_BAR();
-      HMMC_STAMP();
-      // phase 2
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) b1f[ks][j] = read_frag<BK, 128>(base + 3 * HALF, brow + j * 16, ks, lane);
-      HMMC_ST2();
-      asm volatile(HMMC_VMW ::: "memory");
-      HMMC_BAR();
-      HMMC_MM(0, 2, b1f);
-      HMMC_BAR();
-      HMMC_STAMP();
-      // phase 3
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) af[ks][i] = read_frag<AK, 128>(base + HALF, arow + i * 16, ks, lane);
-      HMMC_ST3();
-      asm volatile(HMMC_VMW ::: "memory");
-      HMMC_BAR();
-      HMMC_MM(4, 2, b1f);
-      HMMC_BAR();
-      HMMC_STAMP();
-      // phase 4
-      HMMC_ST4();
-      asm volatile(HMMC_VMW ::: "memory");
-      HMMC_BAR();
-      HMMC_MM(4, 0, b0f);
-      HMMC_BAR();
-      HMMC_STAMP();
-#endif
       int n_item, n_split, n_tm, n_tn, n_kt, n_end;
       next_pos(n_item, n_split, n_tm, n_tn, n_kt, n_end);
       if (kt + 1 >= kt_end) {
@@ -830,12 +721,6 @@ __device__ __forceinline__ void gemm_f16_body(const GemmArgs& p, const GemmGroup
 #undef HMMC_BAR
 #undef HMMC_MM
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // trailing out-of-range DMA must land before the LDS is released
-#if HMMC_DBG >= 3
-    if (p.ws) {
-      unsigned* so = reinterpret_cast<unsigned*>(p.ws) + ((size_t)bid * 8 + wid) * 128;
-      so[lane] = st0; so[64 + lane] = st1;
-    }
-#endif
   } else {
     // ---- 128x128 tile, two workgroups per CU overlap each other: simple two-barrier loop
     while (true) {
@@ -1029,7 +914,7 @@ std::mutex g_prof_mu;                 // hmmc_gemm_f16 may be called from severa
 std::vector<GemmProfRec> g_prof;
 }  // namespace
 
-// launch sites of other translation units (gemm_f32.hip): see options.h
+// every timed launch site (gemm_f16_one, the grouped weight gradients, hmmc_gemm_f32) brackets its kernels with these: see options.h
 long hmmc_prof_begin(double flops, double bytes, int slot, hipStream_t stream) {
   if (!g_prof_on) return -1;
   GemmProfRec rec{};
@@ -1180,18 +1065,13 @@ static int gemm_f16_one(const void* A, const void* B, void* C, int M, int N, int
   const int cus = gemm_cus();
   long resident = (long)cus * (cfg.bm == 256 ? 1 : 2);          // workgroups the LDS budget keeps resident
   dim3 grid((unsigned)(items < resident ? items : resident));
-  GemmProfRec rec{};
-  if (g_prof_on) {
-    (void)hipEventCreate(&rec.e0); (void)hipEventCreate(&rec.e1);
-    rec.flops = 2.0 * M * N * K;
-    double mn = (double)M * N;
-    rec.bytes = 2.0 * ((double)M * K + (double)N * K + mn) + ((epilogue & EPI_BIAS) ? 2.0 * N : 0.0) +
-                2.0 * mn * (((epilogue & EPI_RESID) ? 1 : 0) + ((epilogue & (EPI_DGELU | EPI_MULAUX)) ? 1 : 0) + (aux_out ? 1 : 0));
-    if (epilogue & EPI_LNFOLD) rec.bytes += 8.0 * M + 8.0 * N;
-    if (epilogue & EPI_ROWSTAT) rec.bytes += 8.0 * M * (N / 64);
-    rec.layout = a_kmajor ? (b_kmajor ? 0 : 1) : 2;
-    (void)hipEventRecord(rec.e0, stream);
-  }
+  // bench.py's live timing (off unless hmmc_gemm_profile_start was called): slot 0-2 by operand layout
+  const double mn = (double)M * N;
+  double bytes = 2.0 * ((double)M * K + (double)N * K + mn) + ((epilogue & EPI_BIAS) ? 2.0 * N : 0.0) +
+                 2.0 * mn * (((epilogue & EPI_RESID) ? 1 : 0) + ((epilogue & (EPI_DGELU | EPI_MULAUX)) ? 1 : 0) + (aux_out ? 1 : 0));
+  if (epilogue & EPI_LNFOLD) bytes += 8.0 * M + 8.0 * N;
+  if (epilogue & EPI_ROWSTAT) bytes += 8.0 * M * (N / 64);
+  const long tok = hmmc_prof_begin(2.0 * M * N * K, bytes, a_kmajor ? (b_kmajor ? 0 : 1) : 2, stream);
   if (cfg.bm == 256) launch_cfg<256, 256, 2, 4>(p, a_kmajor, b_kmajor, grid, stream);
   else launch_cfg<128, 128, 2, 2>(p, a_kmajor, b_kmajor, grid, stream);
   if (splitk > 1 && !slab_mode) {
@@ -1200,7 +1080,7 @@ static int gemm_f16_one(const void* A, const void* B, void* C, int M, int N, int
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, (const float*)workspace, (half_t*)C, M, N,
                        ldc, splitk);
   }
-  if (rec.e0) { (void)hipEventRecord(rec.e1, stream); std::lock_guard<std::mutex> lk(g_prof_mu); g_prof.push_back(rec); }
+  hmmc_prof_end(tok, stream);
   return hmmc_launch_status();
 }
 
@@ -1294,16 +1174,11 @@ extern "C" int hmmc_gemm_f16_wgrad_group(const void* const* dY, const void* cons
   constexpr int SMEM = 2 * (256 + 256) * BKT * 2 + 8 * EPI_LDS_PER_WAVE;
   static bool done[HMMC_MAX_DEVICES] = {false};
   hmmc_allow_lds((const void*)gemm_f16_wgrad_group_kernel, SMEM, done);
-  GemmProfRec rec{};
-  if (g_prof_on) {
-    (void)hipEventCreate(&rec.e0); (void)hipEventCreate(&rec.e1);
-    rec.flops = flops; rec.bytes = bytes; rec.layout = 2;
-    (void)hipEventRecord(rec.e0, stream);
-  }
+  const long tok = hmmc_prof_begin(flops, bytes, 2, stream);
   hipLaunchKernelGGL(gemm_f16_wgrad_group_kernel, dim3((unsigned)(items < cus ? items : cus)), dim3(512), SMEM, stream, p, gp);
   const size_t nb = ((size_t)e0 / 4 + 255) / 256;
   hipLaunchKernelGGL(splitk_reduce_group_kernel, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(256), 0, stream, (const float*)workspace, go);
-  if (rec.e0) { (void)hipEventRecord(rec.e1, stream); std::lock_guard<std::mutex> lk(g_prof_mu); g_prof.push_back(rec); }
+  hmmc_prof_end(tok, stream);
   return hmmc_launch_status();
 }
 

@@ -11,7 +11,6 @@
 // swapped (A-operand = B rows) so a lane owns 4 consecutive n of one row: 16-byte stores.
 #include "common.h"
 #include "options.h"
-#include <cstdlib>
 
 namespace {
 
@@ -643,6 +642,88 @@ void launch_f32(int bmode, dim3 grid, hipStream_t stream, const G32& p) {
   }
 }
 
+// bytes from the first to the last element of a rows x K operand (one of its two strides is 1)
+inline uint64_t f32_extent(int rows, int K, long s_row, long s_k) {
+  return (s_k == 1 ? (uint64_t)(rows - 1) * s_row + K : (uint64_t)(K - 1) * s_k + rows) * 4;
+}
+
+// The LDS-DMA kernel on (32 mi) x 64 tiles
+template <bool AKC, bool BKC>
+void launch_f32_dma(const G32& p, int mi, hipStream_t stream) {
+  const long tiles = (long)((p.M + 32 * mi - 1) / (32 * mi)) * ((p.N + 63) / 64);
+  const int smem = 3 * (32 * mi + 64) * 32 * 4;
+  const int a_fast = (long)p.M < (long)p.N;                     // A is the smaller operand: walk its tiles fastest
+  auto k = mi == 1 ? gemm_f32_dma_kernel<AKC, BKC, 1> : gemm_f32_dma_kernel<AKC, BKC, 2>;
+  hipLaunchKernelGGL(k, dim3((unsigned)tiles), dim3(256), smem, stream, p, (unsigned)f32_extent(p.M, p.K, p.sam, p.sak),
+                     (unsigned)f32_extent(p.N, p.K, p.sbn, p.sbk), a_fast);
+}
+
+// The wave-split-K kernel on (16 rm) x 64 tiles
+template <bool AV, bool BV>
+void launch_f32_wavek(const G32& p, int rm, hipStream_t stream) {
+  void (*k)(G32);
+  if (rm == 2) k = gemm_f32_wavek_kernel<AV, BV, 2, 4>;
+  else if (rm == 3) k = gemm_f32_wavek_kernel<AV, BV, 3, 4>;
+  else if (rm == 4) k = gemm_f32_wavek_kernel<AV, BV, 4, 4>;
+  else k = gemm_f32_wavek_kernel<AV, BV, 6, 4>;
+  const long tiles = (long)((p.M + 16 * rm - 1) / (16 * rm)) * ((p.N + 63) / 64);
+  const int smem = 4 * rm * 4 * 1024;
+  static bool done[HMMC_MAX_DEVICES] = {false};                 // the LDS opt-in of the rm = 6 kernel, the only one above 64 KiB
+  if (smem > 64 * 1024) hmmc_allow_lds((const void*)k, smem, done);
+  hipLaunchKernelGGL(k, dim3((unsigned)tiles), dim3(256), smem, stream, p);
+}
+
+enum F32Kind { F32_SMALL, F32_TILED, F32_WAVEK, F32_DMA };
+struct F32Plan { F32Kind kind; int rm, mi; };                   // rm: wave-split-K tile rows / 16; mi: LDS-DMA tile rows / 32
+
+// The fp32 kernel with the least estimated time for the problem in p (operands, strides, avec / bvec filled in).
+F32Plan plan_f32(const G32& p, int num_cu, bool no_wavek, bool no_dma) {
+  const int M = p.M, N = p.N, K = p.K;
+  const long blocks = (long)((M + TM - 1) / TM) * ((N + TN - 1) / TN);
+  // Two kernels.  The 64x64 LDS kernel runs one 16-deep K-step per ~0.4 us while a workgroup is alone on its CU (0.2 us of
+  // MFMA plus the in-order issue of its staging and the barrier) and ~0.6x that per further co-resident workgroup, so a
+  // problem with few tiles is bound by the length of K; the split-K 16x32 kernel has no such chain but re-reads its operands
+  // from L2 for every 16x32 tile (0.19 B/flop; both operands k-contiguous cost more because a 16-byte load then touches 16
+  // rows).  Estimated times in us (fitted to measurements at 96..3072 rows of the temporal-transformer shapes) pick one.
+  const double mnk = (double)M * N * K;
+  const double t_small = 3.0 + mnk * ((p.sak == 1 && p.sbk == 1) ? 6.0e-8 : 3.9e-8);
+  // (many tiles per CU: the 64x64 kernel settles at one tile per CU per K/16 x 0.333 us - the MLM head's 72 tiles per CU)
+  const double t_tiled_few = 3.0 + (K / 16.0) * 0.40 * (0.4 + 0.6 * (double)((blocks + num_cu - 1) / num_cu));
+  const double t_tiled_many = 3.0 + (K / 16.0) * 0.333 * ((double)blocks / num_cu + 0.5);       // + half a round of imbalance
+  const double t_tiled = t_tiled_few > t_tiled_many ? t_tiled_few : t_tiled_many;
+  F32Plan plan{t_small < t_tiled ? F32_SMALL : F32_TILED, 0, 0};
+  double best = t_small < t_tiled ? t_small : t_tiled;
+  // The wave-split-K kernel on (16 RM) x 64 tiles, for problems it covers with at most one workgroup per CU (more than one per CU
+  // share the matrix pipe at ~0.7 of its rate: measured).  Matrix-rate bound: 2 RM RN K cycles per tile; the smallest RM that
+  // fits the CUs gives the shortest chain.  Measured against the other two kernels on every fp32 shape of the path: ahead for
+  // K >= 1536 (data / weight gradients and c_proj of the temporal transformer, the MoCo query gradient, the MLM data gradient),
+  // behind for K = 512, where the fixed ~6 us of fill and reduction decide.
+  static const int rms[4] = {2, 3, 4, 6};
+  for (int c = 0; c < 4 && !no_wavek; ++c) {
+    const long tiles = (long)((M + 16 * rms[c] - 1) / (16 * rms[c])) * ((N + 63) / 64);
+    if (tiles > num_cu) continue;
+    const double t = 6.0 + (double)K * rms[c] * 4 * (2.0 / 1900.0) / 0.85;
+    if (t < best) { best = t; plan = F32Plan{F32_WAVEK, rms[c], 0}; }
+    break;                                                                        // larger tiles only lengthen the chain
+  }
+  // The LDS-DMA kernel (16-byte aligned rows on both sides, whole 32-deep K-steps, 32-bit byte offsets): (32 MI) x 64 tiles,
+  // three (MI = 2) or four (MI = 1) workgroups per CU.  Measured on the temporal transformer at 3 072 tokens and the
+  // pre-training heads (scratch/gemm32_dma.py): ~8-10 us of launch, fill and drain + rounds x the tile's time at 0.78 (64x64) /
+  // 0.71 (32x64) of the matrix rate; ahead of the kernels above wherever there are several tiles per CU.
+  const uint64_t a_reach = (p.sak == 1 ? (uint64_t)(M + 64) * p.sam : (uint64_t)K * p.sak + M + 64) * 4;
+  const uint64_t b_reach = (p.sbk == 1 ? (uint64_t)(N + 64) * p.sbn : (uint64_t)K * p.sbk + N + 64) * 4;
+  const bool dma_ok = p.avec && p.bvec && !(K & 31) && f32_extent(M, K, p.sam, p.sak) < (1ull << 31) &&
+                      f32_extent(N, K, p.sbn, p.sbk) < (1ull << 31) && a_reach < 0xfffffff0ull && b_reach < 0xfffffff0ull;
+  for (int c = 1; c <= 2 && dma_ok && !no_dma; ++c) {
+    const long tiles = (long)((M + 32 * c - 1) / (32 * c)) * ((N + 63) / 64);
+    const double tile_us = 32.0 * c * 64 * K * 2 / (256.0 * 2400.0);            // one tile at the CU's full f32 matrix rate
+    if (tiles < 2 * num_cu) continue;                                           // alone on its CU a workgroup hides nothing: 0.6 of the rate
+    const double t = 8.0 + (double)((tiles + num_cu - 1) / num_cu) * tile_us / (c == 2 ? 0.78 : 0.71);
+    if (t < best) { best = t; plan = F32Plan{F32_DMA, 0, c}; }
+  }
+  return plan;
+}
+
 }  // namespace
 
 static int gemm_f32_impl(const float* A, const float* B, float* C, int M, int N, int K, long sam, long sak, long sbk,
@@ -679,114 +760,42 @@ static int gemm_f32_impl(const float* A, const float* B, float* C, int M, int N,
   p.avec = !(a_ld & 3) && !((uintptr_t)A & 15);
   p.bvec = !(b_ld & 3) && !((uintptr_t)B & 15);
   p.cvec = !(ldc & 3) && !((uintptr_t)C & 15) && (!aux_out || !((uintptr_t)aux_out & 15));
-  long blocks = (long)((M + TM - 1) / TM) * ((N + TN - 1) / TN);
-  const int num_cu = hmmc_num_cus();
-  // Two kernels.  The 64x64 LDS kernel runs one 16-deep K-step per ~0.4 us while a workgroup is alone on its CU (0.2 us of
-  // MFMA plus the in-order issue of its staging and the barrier) and ~0.6x that per further co-resident workgroup, so a
-  // problem with few tiles is bound by the length of K; the split-K 16x32 kernel has no such chain but re-reads its operands
-  // from L2 for every 16x32 tile (0.19 B/flop; both operands k-contiguous cost more because a 16-byte load then touches 16
-  // rows).  Estimated times in us (fitted to measurements at 96..3072 rows of the temporal-transformer shapes) pick one.
-  const double mnk = (double)M * N * K;
-  const double t_small = 3.0 + mnk * ((sak == 1 && sbk == 1) ? 6.0e-8 : 3.9e-8);
-  // (many tiles per CU: the 64x64 kernel settles at one tile per CU per K/16 x 0.333 us - the MLM head's 72 tiles per CU)
-  const double t_tiled_few = 3.0 + (K / 16.0) * 0.40 * (0.4 + 0.6 * (double)((blocks + num_cu - 1) / num_cu));
-  const double t_tiled_many = 3.0 + (K / 16.0) * 0.333 * ((double)blocks / num_cu + 0.5);       // + half a round of imbalance
-  const double t_tiled = t_tiled_few > t_tiled_many ? t_tiled_few : t_tiled_many;
-  // The wave-split-K kernel on (16 RM) x 64 tiles, for problems it covers with at most one workgroup per CU (more than one per CU
-  // share the matrix pipe at ~0.7 of its rate: measured).  Matrix-rate bound: 2 RM RN K cycles per tile; the smallest RM that
-  // fits the CUs gives the shortest chain.  Measured against the other two kernels on every fp32 shape of the path
-  // (scratch/gemm32_pick.py): ahead for K >= 1536 (data / weight gradients and c_proj of the temporal transformer, the MoCo
-  // query gradient, the MLM data gradient), behind for K = 512, where the fixed ~6 us of fill and reduction decide.
-  {
-    const bool off = hmmc_option(HMMC_OPT_NO_F32_WAVEK);                          // A/B runs
-#ifdef HMMC_SCRATCH      // scratch/gemm32_pick.py builds: HMMC_F32_PICK = 1 small, 2 tiled, 3.. wave-split-K RM = 2, 3, 4, 6,
-    static const char* force_s = std::getenv("HMMC_F32_PICK");                    // 7 / 9 LDS-DMA 64x64 / 32x64
-    const int force = force_s ? atoi(force_s) : 0;
-#else
-    const int force = 0;
-#endif
-    const bool av = sak == 1 && p.avec && !(K & 3), bv = sbk == 1 && p.bvec && !(K & 3);
-    static const int rms[4] = {2, 3, 4, 6};
-    double best = t_small < t_tiled ? t_small : t_tiled;
-    int rm = 0;
-    if (force >= 3 && force <= 6) rm = rms[force - 3];
-    for (int c = 0; c < 4 && !off && !force; ++c) {
-      const long tiles = (long)((M + 16 * rms[c] - 1) / (16 * rms[c])) * ((N + 63) / 64);
-      if (tiles > num_cu) continue;
-      const double t = 6.0 + (double)K * rms[c] * 4 * (2.0 / 1900.0) / 0.85;
-      if (t < best) { best = t; rm = rms[c]; }
-      break;                                                                      // larger tiles only lengthen the chain
+  const F32Plan plan = plan_f32(p, hmmc_num_cus(), hmmc_option(HMMC_OPT_NO_F32_WAVEK), hmmc_option(HMMC_OPT_NO_F32_DMA));
+  // 16-byte k-contiguous operand loads of the wave-split-K and small kernels
+  const bool av = sak == 1 && p.avec && !(K & 3), bv = sbk == 1 && p.bvec && !(K & 3);
+  switch (plan.kind) {
+    case F32_DMA: {
+      const bool akc = sak == 1, bkc = sbk == 1;
+      if (akc && bkc) launch_f32_dma<true, true>(p, plan.mi, stream);
+      else if (akc) launch_f32_dma<true, false>(p, plan.mi, stream);
+      else if (bkc) launch_f32_dma<false, true>(p, plan.mi, stream);
+      else launch_f32_dma<false, false>(p, plan.mi, stream);
+      break;
     }
-    // The LDS-DMA kernel (16-byte aligned rows on both sides, whole 32-deep K-steps, 32-bit byte offsets): (32 MI) x 64 tiles,
-    // three (MI = 2) or four (MI = 1) workgroups per CU.  Measured on the temporal transformer at 3 072 tokens and the
-    // pre-training heads (scratch/gemm32_dma.py): ~8-10 us of launch, fill and drain + rounds x the tile's time at 0.78 (64x64) /
-    // 0.71 (32x64) of the matrix rate; ahead of the kernels above wherever there are several tiles per CU.
-    {
-      const uint64_t a_ext = (sak == 1 ? (uint64_t)(M - 1) * sam + K : (uint64_t)(K - 1) * sak + M) * 4;
-      const uint64_t b_ext = (sbk == 1 ? (uint64_t)(N - 1) * sbn + K : (uint64_t)(K - 1) * sbk + N) * 4;
-      const uint64_t a_reach = (sak == 1 ? (uint64_t)(M + 64) * sam : (uint64_t)K * sak + M + 64) * 4;
-      const uint64_t b_reach = (sbk == 1 ? (uint64_t)(N + 64) * sbn : (uint64_t)K * sbk + N + 64) * 4;
-      const bool dma_ok = p.avec && p.bvec && !(K & 31) && a_ext < (1ull << 31) && b_ext < (1ull << 31) && a_reach < 0xfffffff0ull &&
-                          b_reach < 0xfffffff0ull;
-      const bool dma_off = hmmc_option(HMMC_OPT_NO_F32_DMA);                      // A/B runs
-      int mi = 0;
-      if (dma_ok && (force == 7 || force == 9)) mi = force == 7 ? 2 : 1;
-      for (int c = 1; c <= 2 && dma_ok && !dma_off && !force; ++c) {
-        const long tiles = (long)((M + 32 * c - 1) / (32 * c)) * ((N + 63) / 64);
-        const double tile_us = 32.0 * c * 64 * K * 2 / (256.0 * 2400.0);          // one tile at the CU's full f32 matrix rate
-        if (tiles < 2 * num_cu) continue;                                         // alone on its CU a workgroup hides nothing: 0.6 of the rate
-        const double t = 8.0 + (double)((tiles + num_cu - 1) / num_cu) * tile_us / (c == 2 ? 0.78 : 0.71);
-        if (t < best) { best = t; mi = c; rm = 0; }
+    case F32_WAVEK:
+      if (av && bv) launch_f32_wavek<true, true>(p, plan.rm, stream);
+      else if (av) launch_f32_wavek<true, false>(p, plan.rm, stream);
+      else if (bv) launch_f32_wavek<false, true>(p, plan.rm, stream);
+      else launch_f32_wavek<false, false>(p, plan.rm, stream);
+      break;
+    case F32_SMALL: {
+      const long small = (long)((M + 15) / 16) * ((N + 31) / 32);
+      auto k = av ? (bv ? gemm_f32_small_kernel<true, true> : gemm_f32_small_kernel<true, false>)
+                  : (bv ? gemm_f32_small_kernel<false, true> : gemm_f32_small_kernel<false, false>);
+      hipLaunchKernelGGL(k, dim3((unsigned)small), dim3(256), 0, stream, p);
+      break;
+    }
+    case F32_TILED: {
+      const int amode = !p.avec ? OP_SCALAR : sak == 1 ? ((K & 3) ? OP_SCALAR : OP_KVEC) : ((M & 3) ? OP_SCALAR : OP_RVEC);
+      const int bmode = !p.bvec ? OP_SCALAR : sbk == 1 ? ((K & 3) ? OP_SCALAR : OP_KVEC) : ((N & 3) ? OP_SCALAR : OP_RVEC);
+      const dim3 grid((unsigned)((long)((M + TM - 1) / TM) * ((N + TN - 1) / TN)));
+      switch (amode) {
+        case OP_KVEC: launch_f32<OP_KVEC>(bmode, grid, stream, p); break;
+        case OP_RVEC: launch_f32<OP_RVEC>(bmode, grid, stream, p); break;
+        default: launch_f32<OP_SCALAR>(bmode, grid, stream, p); break;
       }
-      if (mi) {
-        const long tiles = (long)((M + 32 * mi - 1) / (32 * mi)) * ((N + 63) / 64);
-        const int smem = 3 * (32 * mi + 64) * 32 * 4;
-        const int a_fast = (long)M < (long)N;                     // A is the smaller operand: walk its tiles fastest
-#define HMMC_DMA1(AKC, BKC, MI_) hipLaunchKernelGGL((gemm_f32_dma_kernel<AKC, BKC, MI_>), dim3((unsigned)tiles), dim3(256), smem, stream, p, \
-                                                    (unsigned)a_ext, (unsigned)b_ext, a_fast)
-#define HMMC_DMA(AKC, BKC) do { if (mi == 1) HMMC_DMA1(AKC, BKC, 1); else HMMC_DMA1(AKC, BKC, 2); } while (0)
-        const bool akc = sak == 1, bkc = sbk == 1;
-        if (akc && bkc) HMMC_DMA(true, true); else if (akc) HMMC_DMA(true, false); else if (bkc) HMMC_DMA(false, true); else HMMC_DMA(false, false);
-#undef HMMC_DMA
-#undef HMMC_DMA1
-        return hmmc_launch_status();
-      }
+      break;
     }
-    if (rm) {
-      const long tiles = (long)((M + 16 * rm - 1) / (16 * rm)) * ((N + 63) / 64);
-      const int smem = 4 * rm * 4 * 1024;
-#define HMMC_WK1(AVV, BVV, RMM) do { static bool done_[HMMC_MAX_DEVICES] = {false}; \
-        if (smem > 64 * 1024) hmmc_allow_lds((const void*)gemm_f32_wavek_kernel<AVV, BVV, RMM, 4>, smem, done_); \
-        hipLaunchKernelGGL((gemm_f32_wavek_kernel<AVV, BVV, RMM, 4>), dim3((unsigned)tiles), dim3(256), smem, stream, p); } while (0)
-#define HMMC_WK(AVV, BVV) do { if (rm == 2) HMMC_WK1(AVV, BVV, 2); else if (rm == 3) HMMC_WK1(AVV, BVV, 3); \
-                               else if (rm == 4) HMMC_WK1(AVV, BVV, 4); else HMMC_WK1(AVV, BVV, 6); } while (0)
-      if (av && bv) HMMC_WK(true, true); else if (av) HMMC_WK(true, false); else if (bv) HMMC_WK(false, true); else HMMC_WK(false, false);
-#undef HMMC_WK
-#undef HMMC_WK1
-      return hmmc_launch_status();
-    }
-  }
-#ifdef HMMC_SCRATCH
-  static const char* force2_s = std::getenv("HMMC_F32_PICK");
-  const int force2 = force2_s ? atoi(force2_s) : 0;
-#else
-  const int force2 = 0;
-#endif
-  if (force2 == 1 || (force2 != 2 && t_small < t_tiled)) {
-    long small = (long)((M + 15) / 16) * ((N + 31) / 32);
-    const bool av = sak == 1 && p.avec && !(K & 3), bv = sbk == 1 && p.bvec && !(K & 3);
-    auto k = av ? (bv ? gemm_f32_small_kernel<true, true> : gemm_f32_small_kernel<true, false>)
-                : (bv ? gemm_f32_small_kernel<false, true> : gemm_f32_small_kernel<false, false>);
-    hipLaunchKernelGGL(k, dim3((unsigned)small), dim3(256), 0, stream, p);
-    return hmmc_launch_status();
-  }
-  const int amode = !p.avec ? OP_SCALAR : sak == 1 ? ((K & 3) ? OP_SCALAR : OP_KVEC) : ((M & 3) ? OP_SCALAR : OP_RVEC);
-  const int bmode = !p.bvec ? OP_SCALAR : sbk == 1 ? ((K & 3) ? OP_SCALAR : OP_KVEC) : ((N & 3) ? OP_SCALAR : OP_RVEC);
-  const dim3 grid((unsigned)blocks);
-  switch (amode) {
-    case OP_KVEC: launch_f32<OP_KVEC>(bmode, grid, stream, p); break;
-    case OP_RVEC: launch_f32<OP_RVEC>(bmode, grid, stream, p); break;
-    default: launch_f32<OP_SCALAR>(bmode, grid, stream, p); break;
   }
   return hmmc_launch_status();
 }

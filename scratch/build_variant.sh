@@ -1,6 +1,6 @@
 #!/bin/bash
 # builds scratch/_dbg/libhmmc_<name>.so from the working-tree gemm_f16.hip with extra -D flags (same-box A/B runs):
-#   bash scratch/build_variant.sh sched1 -DHMMC_GEMM_SCHED=1
+#   bash scratch/build_variant.sh mine [-DNAME=VALUE ...]    (e.g. a patched gemm_f16.hip against the committed one)
 set -e
 cd /root/repo
 name=$1; shift

@@ -1,6 +1,6 @@
 #!/bin/bash
 # builds scratch/_dbg/libhmmc_<name>.so with ONE source of hmmc_amd/csrc rebuilt from the working tree with extra -D flags:
-#   bash scratch/build_variant_src.sh attention_f16 noP0 -DHMMC_SCRATCH -DHMMC_ATTN_ABL=1
+#   bash scratch/build_variant_src.sh attention_f16 mine [-DNAME=VALUE ...]
 set -e
 cd /root/repo
 src=$1; name=$2; shift 2

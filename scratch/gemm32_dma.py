@@ -1,5 +1,5 @@
-"""fp32 GEMM kernels by shape: time and max error against a float64 product.  HMMC_F32_PICK (a -DHMMC_SCRATCH build named by
-HMMC_LIB) forces one kernel: 0 dispatcher, 2 64x64 register-staged, 7 / 8 LDS-DMA 64x64 / 128x64.  usage: python scratch/gemm32_dma.py [tokens]"""
+"""fp32 GEMM by shape, as the dispatcher picks the kernel: time and max error against a float64 product (HMMC_LIB: a variant
+build).  usage: python scratch/gemm32_dma.py [tokens]"""
 import sys, os, torch
 sys.path.insert(0, '/root/repo')
 from hmmc_amd import _lib

@@ -54,11 +54,14 @@ def test_options_and_release_entry_points(monkeypatch):
     with pytest.raises(KeyError):
         _lib.set_option("nope", 1)
     assert lib.hmmc_tower_release(None, None) == 0           # nothing cached in a process that never ran a tower backward
-    # no getenv in the product sources (the scratch-only HMMC_F32_PICK sits behind #ifdef HMMC_SCRATCH)
+    # no getenv in the product sources, and none of the removed build-time experiment switches
     import glob
+    removed = ("HMMC_SCRATCH", "HMMC_DBG", "HMMC_PHASES", "HMMC_PF", "HMMC_ATTN_SKIP", "HMMC_ATTN_PIN", "HMMC_ATTN_ABL",
+               "HMMC_ATTN_FWD_WPB", "HMMC_F32_PICK")
     for src in glob.glob(os.path.join(ROOT, "hmmc_amd", "csrc", "*.hip")) + glob.glob(os.path.join(ROOT, "hmmc_amd", "csrc", "*.h")):
-        text = re.sub(r"#ifdef HMMC_SCRATCH.*?#e(lse|ndif)", "", open(src).read(), flags=re.S)
+        text = open(src).read()
         assert "getenv" not in text, src
+        assert not [m for m in removed if re.search(rf"\b{m}\b", text)], src
     # a variable that is present - even empty - switches its option on when the library is loaded
     monkeypatch.setenv("HMMC_NO_F32_WAVEK", "")
     monkeypatch.setattr(_lib, "_lib", None)

@@ -99,7 +99,7 @@ def test_gemm_f32_many_tiles_exact_integers(M, N, K):
     of its 64x64 or 32x64 tiles per CU: the temporal transformer at 3 072 tokens, the MoCo projector and logits, the MLM head;
     reference modules/module_cross.py:114-149, modules/modeling.py:286-313,788-807), with ragged M / N edges, in the orientations
     of the path and with every epilogue.  Integer-valued operands: every product and partial sum is exact in fp32, so the result
-    must EQUAL the fp64 product.  (scratch/fuzz_f32_dma.py forces the kernel on 150 random shapes per tile size: no mismatch.)"""
+    must EQUAL the fp64 product.  (The kernel forced on 150 random shapes per tile size: no mismatch.)"""
     g = torch.Generator().manual_seed(M + N + K)
     a = torch.randint(-3, 4, (M, K), generator=g).float().to(DEV)
     b = torch.randint(-3, 4, (N, K), generator=g).float().to(DEV)

@@ -688,3 +688,87 @@ class LooseSimFn(torch.autograd.Function):
         dqn = ops.gemm_f32(dS, vn, nq, E, nv, (nv, 1), (E, 1), alpha=ctx.scale)          # dS @ vn
         dvn = ops.gemm_f32(dS, qn, nv, E, nq, (1, nv), (E, 1), alpha=ctx.scale)          # dS^T @ qn
         return ops.l2norm_bwd(dqn, qn, qnorm), ops.l2norm_bwd(dvn, vn, vnorm), None
+
+
+def bert_seed():
+    """A fresh 62-bit dropout seed from torch's default (host) generator: torch.manual_seed reproduces a run, no device sync."""
+    return int(torch.randint(0, 1 << 62, (1,), dtype=torch.int64).item())
+
+
+def _bert_tower_forward(ids, mask, params, cfg, keep):
+    """hmmc_bert_fwd: -> (last_hidden_state [b*L, D], acts or None)."""
+    from ._lib import call, ptr, query
+    heads, inter, eps, p_hidden, p_attn, seed = cfg
+    b, L = ids.shape
+    vocab, D = params[0].shape
+    nl = (len(params) - ops.BERT_EMB_PARAMS) // ops.BERT_LAYER_PARAMS
+    acts = torch.empty(query("hmmc_bert_act_bytes", b, L, heads, D, inter, nl, int(keep), int(p_attn > 0)), dtype=torch.uint8,
+                       device=ids.device)
+    y = torch.empty((b * L, D), dtype=torch.float32, device=ids.device)
+    call("hmmc_bert_fwd", ptr(ids), ptr(mask), ptr(y), _ptr_array(params), ptr(acts), int(keep), b, L, heads, D, inter, nl, vocab,
+         float(eps), float(p_hidden), float(p_attn), int(seed), ptr(ops.device_error_flag(ids.device)))
+    return y, (acts if keep else None)
+
+
+def _bert_tower_backward(dy, ids, mask, params, acts, cfg):
+    from ._lib import call, ptr, query
+    heads, inter, eps, p_hidden, p_attn, seed = cfg
+    b, L = ids.shape
+    vocab, D = params[0].shape
+    nl = (len(params) - ops.BERT_EMB_PARAMS) // ops.BERT_LAYER_PARAMS
+    grads = [torch.empty_like(p) for p in params]
+    scratch = torch.empty(query("hmmc_bert_bwd_scratch_bytes", b, L, D, inter), dtype=torch.uint8, device=dy.device)
+    wsb = query("hmmc_bert_workspace_bytes", b, L, D, inter)
+    ws = ops.workspace(wsb, dy.device, "bert")
+    call("hmmc_bert_bwd", ptr(dy), ptr(ids), ptr(mask), _ptr_array(params), _ptr_array(grads), ptr(acts), ptr(scratch), b, L, heads, D,
+         inter, nl, vocab, params[1].shape[0], params[2].shape[0], float(p_hidden), float(p_attn), int(seed), ptr(ws), wsb)
+    return grads
+
+
+class BertFn(torch.autograd.Function):
+    """The Chinese text tower in one autograd node (reference modules/module_cross.py:273-277): BertModel(ids, attention_mask),
+    then text_proj of the pooler output (want = "feat" -> [b, E]) or of every hidden row (want = "hidden" -> [b, L, E]).  fp32
+    throughout.  cfg = (heads, intermediate size, LayerNorm eps, p_hidden, p_attn, seed); params: hmmc_bert_fwd's order."""
+
+    @staticmethod
+    def forward(ctx, ids, mask, cfg, want, keep, pool_w, pool_b, proj_w, proj_b, *params):
+        for prm in (pool_w, pool_b, proj_w, proj_b) + params:
+            if prm.dtype != torch.float32 or not prm.is_cuda or not prm.is_contiguous():
+                raise TypeError("the Chinese text encoder runs in fp32 on contiguous CUDA parameters")
+        b, L = ids.shape
+        y, acts = _bert_tower_forward(ids, mask, params, cfg, keep)
+        pooled = None
+        if want == "feat":
+            pooled = ops.bert_pooler_fwd(y, pool_w, pool_b, b, L)
+            out = ops.linear_f32(pooled, proj_w, bias=proj_b)
+        else:
+            out = ops.linear_f32(y, proj_w, bias=proj_b).view(b, L, -1)
+        if keep:
+            ctx.save_for_backward(ids, mask, y, pooled, pool_w, proj_w)
+            ctx.acts, ctx.params, ctx.cfg, ctx.want = acts, params, cfg, want
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        ids, mask, y, pooled, pool_w, proj_w = ctx.saved_tensors
+        b, L = ids.shape
+        d = dout.contiguous().view(-1, dout.shape[-1])
+        dproj_b = ops.colsum(d)
+        dpool_w = dpool_b = None
+        if ctx.want == "feat":
+            dproj_w = ops.wgrad_f32(d, pooled)
+            dpooled = ops.dgrad_f32(d, proj_w)
+            dy = torch.zeros_like(y)                       # no gradient reaches the other rows of last_hidden_state
+            dpool_w, dpool_b = ops.bert_pooler_bwd(dpooled, pooled, y, pool_w, b, L, dy)
+        else:
+            dproj_w = ops.wgrad_f32(d, y)
+            dy = ops.dgrad_f32(d, proj_w)
+        grads = _bert_tower_backward(dy, ids, mask, ctx.params, ctx.acts, ctx.cfg)
+        ctx.acts = None
+        return (None, None, None, None, None, dpool_w, dpool_b, dproj_w, dproj_b, *grads)
+
+
+def bert_text(ids, mask, cfg, want, pool_w, pool_b, proj_w, proj_b, *params):
+    """BertFn.apply; a pass that records no graph (torch.no_grad(): eval) keeps no activations."""
+    keep = torch.is_grad_enabled() and any(p.requires_grad for p in (pool_w, pool_b, proj_w, proj_b) + params)
+    return BertFn.apply(ids, mask, cfg, want, keep, pool_w, pool_b, proj_w, proj_b, *params)

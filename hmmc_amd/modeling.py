@@ -97,12 +97,11 @@ class CLIP4ClipPreTrainedModel(PreTrainedModel, nn.Module):
         cross_config, _ = CrossConfig.get_config(cross_model_name, cache_dir, type_vocab_size, state_dict=None,
                                                  task_config=task_config)
         if state_dict is not None and "visual_encoder.visual.conv1.weight" in state_dict:
-            from . import synth
             clip_sd = {}
             for k, v in state_dict.items():
                 if k.startswith("visual_encoder.visual."):
                     clip_sd["visual." + k[len("visual_encoder.visual."):]] = v
-                elif k.startswith("text_encoder."):
+                elif k.startswith("text_encoder.") and not k.startswith(("text_encoder.chinese_encoder.", "text_encoder.text_proj.")):
                     clip_sd[k[len("text_encoder."):]] = v
             clip_sd["logit_scale"] = torch.tensor(math.log(100.0))
             cross_config._clip_state_dict = clip_sd
@@ -123,6 +122,10 @@ class BirdPreTrainedModel(CLIP4ClipPreTrainedModel):
 
     def __init__(self, cross_config, task_config):
         super(BirdPreTrainedModel, self).__init__(cross_config)
+        if getattr(task_config, "language", "english") == "chinese":
+            raise NotImplementedError("pre-training with language = \"chinese\" is not implemented: the MLM head needs the "
+                                      "BertTokenizer vocabulary (size, [MASK] / [PAD] / [CLS] ids) and TextEncoder.encode_many "
+                                      "needs attention masks; fine-tuning and eval (BirdModel) support the Chinese encoder")
         self.task_config = task_config
         self.rank = task_config.local_rank
         self.mlm_probability = cross_config.mlm_probability
@@ -499,6 +502,8 @@ class BirdModel(BirdPreTrainedModel):
             cur.wait_stream(side)
             query_output.record_stream(cur)
             query_ids.record_stream(side)
+            if torch.is_tensor(query_mask) and query_mask.is_cuda:
+                query_mask.record_stream(side)
         else:
             query_output = self.text_encoder(query_ids, query_mask)
             visual_output, frame_output = self.visual_encoder(video, video_frame)

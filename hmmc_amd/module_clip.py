@@ -225,6 +225,21 @@ def dims_from_state_dict(state_dict, visual_prefix="visual.", text_prefix=""):
                                         if k.startswith(tp + "transformer.resblocks")}))
 
 
+def build_visual(state_dict: dict):
+    """The `visual.*` tensors of a CLIP state_dict -> VisualTransformer with fp16 weights, as build_model leaves it in
+    CLIP.visual.  For state dicts without a CLIP text tower (a checkpoint of the Chinese branch): nothing else is built."""
+    if "visual.proj" not in state_dict:
+        raise NotImplementedError("CLIP ResNet checkpoints are outside the HMMC hot path")
+    vw = state_dict["visual.conv1.weight"].shape[0]
+    vl = len([k for k in state_dict if k.startswith("visual.") and k.endswith(".attn.in_proj_weight")])
+    ps = state_dict["visual.conv1.weight"].shape[-1]
+    grid = round((state_dict["visual.positional_embedding"].shape[0] - 1) ** 0.5)
+    visual = VisualTransformer(ps * grid, ps, vw, vl, vw // 64, state_dict["visual.proj"].shape[1], "2d").float()
+    convert_weights(visual)
+    visual.load_state_dict({k[len("visual."):]: v for k, v in state_dict.items() if k.startswith("visual.")})
+    return visual
+
+
 def build_model(state_dict: dict, local_rank=0):
     """state_dict -> CLIP with fp16 tower weights (reference modules/module_clip.py:530-579)."""
     if "visual.proj" not in state_dict:

@@ -14,7 +14,7 @@ from torch import nn
 
 from . import functional as Fn
 from . import ops
-from .module_clip import CLIP, build_model
+from .module_clip import CLIP, build_model, build_visual
 from .until_module import LayerNorm
 
 logger = logging.getLogger(__name__)
@@ -102,10 +102,14 @@ class VisualEncoder(nn.Module):
 
     def __init__(self, task_config, cross_config):
         super().__init__()
-        _, clip = _clip_for(task_config, cross_config)
         self.use_temp = task_config.use_temp
         self.is_vit = True
-        self.visual = copy.deepcopy(clip.visual)
+        sd = getattr(cross_config, "_clip_state_dict", None)
+        if sd is not None and "token_embedding.weight" not in sd:
+            self.visual = build_visual(sd)          # a checkpoint of the Chinese branch: it holds no CLIP text tower
+        else:
+            _, clip = _clip_for(task_config, cross_config)
+            self.visual = copy.deepcopy(clip.visual)
         if self.use_temp:
             self.temporal_transformer = Transformer(width=cross_config.temporal_hidden_size,
                                                     layers=cross_config.temporal_hidden_layers,
@@ -152,14 +156,102 @@ class VisualEncoder(nn.Module):
         return Fn.LnProjFn.apply(tokens, idx, v.ln_post.weight, v.ln_post.bias, v.proj, tokens.dtype == torch.float16)
 
 
+class _Holder(nn.Module):
+    """Parameter container: a node of the HuggingFace BertModel's module tree (names only; nothing runs here)."""
+
+
+class BertLayerParams(nn.Module):
+    """encoder.layer.N of a HuggingFace BertModel: parameters under the reference's names."""
+
+    def __init__(self, width, inter):
+        super().__init__()
+        self.attention = _Holder()
+        self.attention.self = _Holder()
+        for n in ("query", "key", "value"):
+            setattr(self.attention.self, n, nn.Linear(width, width))
+        self.attention.output = _Holder()
+        self.attention.output.dense = nn.Linear(width, width)
+        self.attention.output.LayerNorm = nn.LayerNorm(width)
+        self.intermediate = _Holder()
+        self.intermediate.dense = nn.Linear(width, inter)
+        self.output = _Holder()
+        self.output.dense = nn.Linear(inter, width)
+        self.output.LayerNorm = nn.LayerNorm(width)
+
+    def flat_params(self):
+        a, o = self.attention, self.output
+        mods = (a.self.query, a.self.key, a.self.value, a.output.dense, a.output.LayerNorm, self.intermediate.dense, o.dense,
+                o.LayerNorm)
+        return [t for m in mods for t in (m.weight, m.bias)]
+
+
+class ChineseBert(nn.Module):
+    """Parameter container with the state_dict of the HuggingFace BertModel the reference loads with AutoModel.from_pretrained
+    (modules/module_cross.py:257-265); executed by functional.BertFn (hmmc_bert_fwd / hmmc_bert_bwd).  `config` is the
+    dict of <pretrained_text>/config.json."""
+
+    def __init__(self, config):
+        super().__init__()
+        w, inter = config["hidden_size"], config["intermediate_size"]
+        self.embeddings = _Holder()
+        self.embeddings.word_embeddings = nn.Embedding(config["vocab_size"], w)
+        self.embeddings.position_embeddings = nn.Embedding(config["max_position_embeddings"], w)
+        self.embeddings.token_type_embeddings = nn.Embedding(config.get("type_vocab_size", 2), w)
+        self.embeddings.LayerNorm = nn.LayerNorm(w)
+        self.encoder = _Holder()
+        self.encoder.layer = nn.ModuleList([BertLayerParams(w, inter) for _ in range(config["num_hidden_layers"])])
+        self.pooler = _Holder()
+        self.pooler.dense = nn.Linear(w, w)
+
+    def flat_params(self):
+        e = self.embeddings
+        out = [e.word_embeddings.weight, e.position_embeddings.weight, e.token_type_embeddings.weight, e.LayerNorm.weight,
+               e.LayerNorm.bias]
+        for layer in self.encoder.layer:
+            out += layer.flat_params()
+        return out
+
+
+def _bert_config(path):
+    """<pretrained_text>/config.json, checked against what the HIP tower implements."""
+    cfg_file = os.path.join(path, "config.json") if path and os.path.isdir(path) else path
+    if not cfg_file or not os.path.exists(cfg_file):
+        raise FileNotFoundError(f"task_config.pretrained_text: no config.json of the Chinese BERT encoder at {path!r}")
+    with open(cfg_file, "r", encoding="utf-8") as fh:
+        cfg = json.load(fh)
+    if cfg.get("position_embedding_type", "absolute") != "absolute":
+        raise NotImplementedError(f"position_embedding_type {cfg['position_embedding_type']!r}: only absolute positions are implemented")
+    if cfg.get("hidden_act", "gelu") != "gelu":
+        raise NotImplementedError(f"hidden_act {cfg['hidden_act']!r}: only the erf-GELU (\"gelu\") is implemented")
+    if cfg["hidden_size"] != 64 * cfg["num_attention_heads"]:
+        raise NotImplementedError("the attention kernels take a head dimension of 64 "
+                                  f"(hidden_size {cfg['hidden_size']}, {cfg['num_attention_heads']} heads)")
+    return cfg
+
+
 class TextEncoder(nn.Module):
-    """CLIP text transformer (english branch; reference modules/module_cross.py:240-305)."""
+    """CLIP text transformer (english) or a BERT encoder + text_proj (chinese); reference modules/module_cross.py:240-305."""
 
     def __init__(self, task_config, cross_config):
         super().__init__()
         self.language = task_config.language
+        if self.language == "chinese":
+            clip_sd = getattr(cross_config, "_clip_state_dict", None)
+            if clip_sd is None:
+                clip_sd = CLIP.get_config(pretrained_clip_name=getattr(task_config, "pretrained_clip_name", None)
+                                          or cross_config.pretrained_clip_name)
+            self.logit_scale = copy.deepcopy(clip_sd["logit_scale"]).float()
+            self.bert_config = _bert_config(getattr(task_config, "pretrained_text", None))
+            self.chinese_encoder = ChineseBert(self.bert_config)
+            self.text_proj = nn.Linear(cross_config.chinese_hidden_size, cross_config.temporal_hidden_size)
+            if cross_config.chinese_hidden_size != self.bert_config["hidden_size"]:
+                raise ValueError(f"cross_config.chinese_hidden_size ({cross_config.chinese_hidden_size}) is not the encoder's "
+                                 f"hidden_size ({self.bert_config['hidden_size']})")
+            self.dtype = torch.float32
+            return
         if self.language != "english":
-            raise NotImplementedError("only the CLIP (english) text transformer is on the HMMC hot path")
+            raise NotImplementedError(f"language {self.language!r}: the text encoder is the CLIP transformer (\"english\") or a "
+                                      "BERT encoder (\"chinese\")")
         clip_state_dict, clip = _clip_for(task_config, cross_config)
         self.logit_scale = copy.deepcopy(clip_state_dict["logit_scale"]).float()    # plain tensor attribute, ln(100)
         self.token_embedding = copy.deepcopy(clip.token_embedding)
@@ -169,8 +261,36 @@ class TextEncoder(nn.Module):
         self.text_projection = copy.deepcopy(clip.text_projection)
         self.dtype = clip.visual.conv1.weight.dtype
 
+    def _forward_chinese(self, input_ids, attention_mask, return_hidden):
+        """BertModel(input_ids, attention_mask) -> text_proj of the pooler output, or of every hidden row (reference
+        modules/module_cross.py:273-277).  Dropout follows self.training, under torch.no_grad() too, as in HuggingFace; the
+        seed of a call comes from torch's default host generator."""
+        cfg = self.bert_config
+        if not input_ids.is_cuda:
+            raise TypeError(f"input_ids: expected a cuda tensor, got {input_ids.device}")
+        b, L = input_ids.shape
+        if L > cfg["max_position_embeddings"]:
+            raise ValueError("sequence longer than the position embedding table")
+        if L > 256:
+            raise ValueError("the masked attention kernels take at most 256 tokens")
+        if attention_mask is None:
+            attention_mask = torch.ones_like(input_ids)
+        if not attention_mask.is_cuda:
+            raise TypeError(f"attention_mask: expected a cuda tensor, got {attention_mask.device}")
+        mask = attention_mask.reshape(b, L).to(torch.int64).contiguous()
+        ph = float(cfg.get("hidden_dropout_prob", 0.0)) if self.training else 0.0
+        pa = float(cfg.get("attention_probs_dropout_prob", 0.0)) if self.training else 0.0
+        seed = Fn.bert_seed() if (ph > 0 or pa > 0) else 0
+        enc = self.chinese_encoder
+        call_cfg = (cfg["num_attention_heads"], cfg["intermediate_size"], float(cfg.get("layer_norm_eps", 1e-12)), ph, pa, seed)
+        return Fn.bert_text(input_ids.to(torch.int64).contiguous(), mask, call_cfg, "hidden" if return_hidden else "feat",
+                            enc.pooler.dense.weight, enc.pooler.dense.bias, self.text_proj.weight, self.text_proj.bias,
+                            *enc.flat_params())
+
     def forward(self, input_ids, attention_mask=None, return_hidden=False):
         bs_pair = input_ids.size(0)
+        if self.language == "chinese":
+            return self._forward_chinese(input_ids.view(bs_pair, -1), attention_mask, return_hidden)
         text_output, hidden = self.encode_text(input_ids, return_hidden=True, _want=("hidden" if return_hidden else "feat"))
         if return_hidden:
             return hidden.view(bs_pair, -1, hidden.size(-1))

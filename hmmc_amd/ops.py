@@ -781,3 +781,112 @@ def ce_bwd_(logits, labels, lse, gout, count):
     gout = gout.contiguous().float()
     call("hmmc_ce_bwd", ptr(logits), ptr(labels), ptr(lse), ptr(gout), ptr(count), R, V)
     return logits
+
+
+# ---------------------------------------------------------------------------- the Chinese text branch (csrc/bert_f32.hip)
+
+BERT_EMB_PARAMS, BERT_LAYER_PARAMS = 5, 16          # pointer order: include/hmmc_hip.h, hmmc_bert_fwd
+
+
+def dropout_fwd(x, p, seed, site, resid=None, out=None):
+    """y = x o keep / (1 - p) (+ resid); the keep mask is a function of (seed, site, element index) alone."""
+    _chk(x, torch.float32, "x")
+    if resid is not None:
+        _chk(resid, torch.float32, "resid")
+        assert resid.numel() == x.numel()
+    y = out if out is not None else torch.empty_like(x)
+    call("hmmc_dropout_fwd", ptr(x), ptr(resid), ptr(y), x.numel(), float(p), int(seed), int(site))
+    return y
+
+
+def dropout_bwd(dy, p, seed, site):
+    _chk(dy, torch.float32, "dy")
+    dx = torch.empty_like(dy)
+    call("hmmc_dropout_bwd", ptr(dy), ptr(dx), dy.numel(), float(p), int(seed), int(site))
+    return dx
+
+
+def bert_embed_fwd(ids, word, pos, type_table, gamma, beta, eps):
+    """LN(word[ids] + pos[:L] + type[0]) -> (y [b*L, D], e, mean, rstd)."""
+    _chk(ids, torch.int64, "ids")
+    for t, n in ((word, "word"), (pos, "pos"), (type_table, "type"), (gamma, "gamma"), (beta, "beta")):
+        _chk(t, torch.float32, n)
+    b, L = ids.shape
+    D = word.shape[1]
+    if L > pos.shape[0]:
+        raise ValueError("sequence longer than the position embedding table")
+    e = torch.empty((b * L, D), dtype=torch.float32, device=ids.device)
+    y = torch.empty_like(e)
+    mean = torch.empty(b * L, dtype=torch.float32, device=ids.device)
+    rstd = torch.empty_like(mean)
+    call("hmmc_bert_embed_fwd", ptr(ids), ptr(word), ptr(pos), ptr(type_table), ptr(gamma), ptr(beta), ptr(e), ptr(y), ptr(mean),
+         ptr(rstd), b * L, L, D, word.shape[0], float(eps), ptr(device_error_flag(ids.device)))
+    return y, e, mean, rstd
+
+
+def bert_embed_bwd(ids, dy, e, gamma, mean, rstd, vocab, max_pos, type_vocab):
+    """-> (dword, dpos, dtype, dgamma, dbeta), every one written whole."""
+    _chk(dy, torch.float32, "dy")
+    b, L = ids.shape
+    D = dy.shape[-1]
+    dev = dy.device
+    de = torch.empty_like(e)
+    dword = torch.empty((vocab, D), dtype=torch.float32, device=dev)
+    dpos = torch.empty((max_pos, D), dtype=torch.float32, device=dev)
+    dtyp = torch.empty((type_vocab, D), dtype=torch.float32, device=dev)
+    dgamma = torch.empty(D, dtype=torch.float32, device=dev)
+    dbeta = torch.empty_like(dgamma)
+    wsb = query("hmmc_bert_embed_bwd_workspace", b * L, L, D)
+    ws = workspace(wsb, dev, "bert")
+    call("hmmc_bert_embed_bwd", ptr(ids), ptr(dy), ptr(e), ptr(gamma), ptr(mean), ptr(rstd), ptr(de), ptr(dword), ptr(dpos), ptr(dtyp),
+         ptr(dgamma), ptr(dbeta), b * L, L, D, vocab, max_pos, type_vocab, ptr(ws), wsb)
+    return dword, dpos, dtyp, dgamma, dbeta
+
+
+def masked_attention_fwd(qkv, key_mask, b, L, H, p=0.0, seed=0, site=0):
+    """-> (out [b*L, 64H], probs [b, H, L, L] after dropout, the softmax itself or None when p == 0)."""
+    _chk(qkv, torch.float32, "qkv")
+    _chk(key_mask, torch.int64, "key_mask")
+    D = H * 64
+    assert tuple(qkv.shape) == (b * L, 3 * D) and tuple(key_mask.shape) == (b, L)
+    out = torch.empty((b * L, D), dtype=torch.float32, device=qkv.device)
+    probs = torch.empty((b, H, L, L), dtype=torch.float32, device=qkv.device)
+    raw = torch.empty_like(probs) if p > 0 else None
+    call("hmmc_masked_attention_fwd", ptr(qkv), ptr(key_mask), ptr(out), ptr(probs), ptr(raw), b, L, H, float(p), int(seed), int(site))
+    return out, probs, raw
+
+
+def masked_attention_bwd(qkv, key_mask, probs, raw, dout, b, L, H, p=0.0, seed=0, site=0):
+    _chk(dout, torch.float32, "dout")
+    assert tuple(dout.shape) == (b * L, H * 64) and (raw is not None or p == 0)
+    dqkv = torch.empty_like(qkv)
+    call("hmmc_masked_attention_bwd", ptr(qkv), ptr(key_mask), ptr(probs), ptr(raw), ptr(dout), ptr(dqkv), b, L, H, float(p), int(seed),
+         int(site))
+    return dqkv
+
+
+def bert_pooler_fwd(x, w, bias, b, L):
+    """tanh(x[class rows] @ w.T + bias): x [b*L, D] -> [b, D]."""
+    _chk(x, torch.float32, "x")
+    _chk(w, torch.float32, "w")
+    _chk(bias, torch.float32, "bias")
+    D = w.shape[0]
+    assert tuple(x.shape) == (b * L, D) and tuple(w.shape) == (D, D)
+    y = torch.empty((b, D), dtype=torch.float32, device=x.device)
+    call("hmmc_bert_pooler_fwd", ptr(x), ptr(w), ptr(bias), ptr(y), b, L * D, D)
+    return y
+
+
+def bert_pooler_bwd(dy, y, x, w, b, L, dx):
+    """dx [b*L, D]: its class rows receive the data gradient, the others are left as they are.  -> (dW, db)."""
+    _chk(dy, torch.float32, "dy")
+    _chk(dx, torch.float32, "dx")
+    D = w.shape[0]
+    assert tuple(dy.shape) == (b, D) and tuple(dx.shape) == (b * L, D)
+    dz = torch.empty_like(dy)
+    dW = torch.empty_like(w)
+    db = torch.empty(D, dtype=torch.float32, device=dy.device)
+    wsb = query("hmmc_colsum_workspace", b, D)
+    ws = workspace(wsb, dy.device, "bert")
+    call("hmmc_bert_pooler_bwd", ptr(dy), ptr(y), ptr(x), ptr(w), ptr(dz), ptr(dx), ptr(dW), ptr(db), b, L * D, D, ptr(ws), wsb)
+    return dW, db

@@ -234,3 +234,97 @@ def pretrain_batch(b, f, title_len=45, tag_len=25, res=224, seed=42, tag="pt"):
     tg, gmask = token_ids(f"{tag}.tag_ids", b, tag_len, seed=seed)
     vid = video(f"{tag}.video", b, f, res, seed=seed)
     return vid, torch.full((b,), f, dtype=torch.long), tg, gmask, title, tmask
+
+
+# ----------------------------------------------------------------------------- the Chinese text branch
+
+@dataclass(frozen=True)
+class BertDims:
+    """config.json of the HuggingFace BertModel behind language = "chinese" (modules/module_cross.py:257-265)."""
+    hidden_size: int = 768
+    num_hidden_layers: int = 12
+    num_attention_heads: int = 12
+    intermediate_size: int = 3072
+    vocab_size: int = 21128
+    max_position_embeddings: int = 512
+    type_vocab_size: int = 2
+    layer_norm_eps: float = 1e-12
+    hidden_dropout_prob: float = 0.0
+    attention_probs_dropout_prob: float = 0.0
+
+    def to_config(self):
+        """What save_pretrained writes and TextEncoder reads (a plain json.load)."""
+        d = asdict(self)
+        d.update(model_type="bert", hidden_act="gelu", position_embedding_type="absolute", pad_token_id=0,
+                 architectures=["BertModel"])
+        return d
+
+
+ZH_BASE = BertDims()                                                        # hfl/chinese-roberta-wwm-ext
+ZH_TINY = BertDims(hidden_size=128, num_hidden_layers=2, num_attention_heads=2, intermediate_size=512, vocab_size=2048,
+                   max_position_embeddings=64)
+ZH_CLS, ZH_SEP, ZH_PAD = 101, 102, 0                                        # BertTokenizer ids of [CLS] / [SEP] / [PAD]
+
+
+def bert_state(dims: BertDims, prefix="text_encoder.", seed=42, embed_dim=512):
+    """chinese_encoder.* (the plain HuggingFace names) and text_proj.*, all fp32, each from its own (seed, name) stream."""
+    sd = {}
+    w, it = dims.hidden_size, dims.intermediate_size
+
+    def put(name, shape, std, mean=0.0):
+        sd[prefix + name] = normal(prefix + name, shape, std, mean, seed=seed)
+
+    def ln(name):
+        put(name + ".weight", (w,), 0.1, 1.0)
+        put(name + ".bias", (w,), 0.05)
+
+    def dense(name, n, k, std):
+        put(name + ".weight", (n, k), std)
+        put(name + ".bias", (n,), 0.02)
+
+    e = "chinese_encoder.embeddings."
+    put(e + "word_embeddings.weight", (dims.vocab_size, w), 0.05)
+    put(e + "position_embeddings.weight", (dims.max_position_embeddings, w), 0.05)
+    put(e + "token_type_embeddings.weight", (dims.type_vocab_size, w), 0.05)
+    ln(e + "LayerNorm")
+    for i in range(dims.num_hidden_layers):
+        p = f"chinese_encoder.encoder.layer.{i}."
+        for n in ("query", "key", "value"):
+            dense(p + "attention.self." + n, w, w, w ** -0.5)
+        dense(p + "attention.output.dense", w, w, 0.5 * w ** -0.5)
+        ln(p + "attention.output.LayerNorm")
+        dense(p + "intermediate.dense", it, w, w ** -0.5)
+        dense(p + "output.dense", w, it, 0.5 * it ** -0.5)
+        ln(p + "output.LayerNorm")
+    dense("chinese_encoder.pooler.dense", w, w, w ** -0.5)
+    dense("text_proj", embed_dim, w, w ** -0.5)
+    return sd
+
+
+def finetune_state_zh(dims: Dims, bdims: BertDims, seed=42, use_temp=True):
+    """BirdModel(language = "chinese") state_dict: the Chinese text encoder beside the CLIP frame tower."""
+    sd = bert_state(bdims, seed=seed, embed_dim=dims.embed_dim)
+    sd.update(visual_encoder_state(dims, seed=seed, use_temp=use_temp))
+    return sd
+
+
+def zh_token_ids(name, b, length, vocab, seed=42, lens=None):
+    """[CLS] + n ids + [SEP] + [PAD]..., with the attention mask of the loader (1 on real tokens).  lens: the number of
+    real tokens per sequence (1 = [CLS] alone); default random in [3, length]."""
+    g = _gen(seed, name)
+    ids = np.zeros((b, length), dtype=np.int64)
+    mask = np.zeros((b, length), dtype=np.int64)
+    for i in range(b):
+        n = int(lens[i]) if lens is not None else int(g.integers(3, length + 1))
+        ids[i, 0] = ZH_CLS
+        if n >= 2:
+            ids[i, 1:n - 1] = g.integers(103, vocab, size=n - 2)
+            ids[i, n - 1] = ZH_SEP
+        mask[i, :n] = 1
+    return torch.from_numpy(ids), torch.from_numpy(mask)
+
+
+def finetune_batch_zh(b, f, length, vocab, res=224, seed=42, tag="zh", lens=None):
+    ids, mask = zh_token_ids(f"{tag}.query_ids", b, length, vocab, seed=seed, lens=lens)
+    vid = video(f"{tag}.video", b, f, res, seed=seed)
+    return ids, mask, vid, torch.full((b,), f, dtype=torch.long), torch.arange(b)

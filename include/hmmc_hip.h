@@ -355,6 +355,74 @@ int hmmc_ce_fwd(const float* logits, const long* labels, float* lse, float* rowl
 int hmmc_ce_bwd(float* logits, const long* labels, const float* lse, const float* grad_out, const float* count, int R, long V,
                 hmmc_stream_t stream);
 
+/* ---- The Chinese text branch (language = "chinese", modules/module_cross.py:257-265,273-277): a HuggingFace BertModel, post-LN,
+ * erf-GELU, LayerNorm eps 1e-12, all fp32 (hmmc_gemm_f32 for every GEMM, nothing rounded to fp16).
+ *
+ * Dropout (BertEmbeddings / BertSelfAttention / BertSelfOutput / BertOutput in train mode).  One counter-based generator,
+ * Philox4x32-10: element idx of site `site` is kept iff word (idx & 3) of Philox(key = seed, counter = (idx >> 2, site)) is
+ * >= p * 2^32 - a pure function of (seed, site, idx), so a backward pass regenerates the mask and none is stored.  The bits
+ * are not those of torch's generator.  hmmc_dropout_fwd: y = x o keep / (1 - p) (+ resid, may be NULL); y may alias x;
+ * n % 4 == 0, 16-byte aligned pointers.  hmmc_dropout_bwd: dx = dy o keep / (1 - p).  p = 0 multiplies nothing: the values
+ * pass through bit for bit (and nothing at all is launched for y == x without resid).  0 <= p < 1. */
+int hmmc_dropout_fwd(const float* x, const float* resid, float* y, long n, float p, long seed, int site, hmmc_stream_t stream);
+int hmmc_dropout_bwd(const float* dy, float* dx, long n, float p, long seed, int site, hmmc_stream_t stream);
+/* BertEmbeddings without its dropout, one pass: e[r] = word[ids[r]] + pos[r % L] + type0 (token type 0, as the reference never
+ * passes token_type_ids), y[r] = LN_eps(e[r]); mean / rstd [rows] and e (may be NULL) are what the backward reads.  D <= 1024,
+ * D % 4 == 0.  An id outside [0, vocab) never indexes the table: its word row counts as zero and *err_flag (device int, may
+ * be NULL) is set, as hmmc_text_embed does.
+ * Backward: de [rows, D] (scratch) receives the LayerNorm backward of dy; dword [vocab, D] (hmmc_text_embed_bwd's owner-row
+ * scheme), dpos [max_pos, D] (row l < L: the sum over sequences; the rest zero), dtype [type_vocab, D] (row 0: the column
+ * sums over all rows; the rest zero), dgamma / dbeta [D] are all WRITTEN, in a fixed summation order.  D % 8 == 0;
+ * rows % L == 0; workspace: hmmc_bert_embed_bwd_workspace bytes. */
+int hmmc_bert_embed_fwd(const long* ids, const float* word, const float* pos, const float* type0, const float* gamma,
+                        const float* beta, float* e, float* y, float* mean, float* rstd, long rows, int L, int D, long vocab,
+                        float eps, int* err_flag, hmmc_stream_t stream);
+size_t hmmc_bert_embed_bwd_workspace(long rows, int L, int D);
+int hmmc_bert_embed_bwd(const long* ids, const float* dy, const float* e, const float* gamma, const float* mean, const float* rstd,
+                        float* de, float* dword, float* dpos, float* dtype, float* dgamma, float* dbeta, long rows, int L, int D,
+                        long vocab, int max_pos, int type_vocab, void* workspace, size_t ws_bytes, hmmc_stream_t stream);
+/* Key-masked fp32 attention, head dim 64, 1 <= L <= 256 (BertSelfAttention with the additive key-padding mask built from
+ * attention_mask): one wave per (sequence, head) up to 64 tokens, one workgroup above; L > 256: HMMC_ERR_UNSUPPORTED.
+ * qkv [b*L, 3*64*H] (Q | K | V), out [b*L, 64*H]; key_mask: int64 [b, L], nonzero = valid key, any pattern.  Masked keys get
+ * probability exactly 0, and their K / V rows are never used, whatever they hold; every query row, padded ones included, is
+ * computed.  A sequence WITHOUT ANY valid key is outside the contract (the reference then attends uniformly; here the row is
+ * undefined).  probs [b, H, L, L]: the probabilities after dropout (dropped and rescaled: what multiplies V); probs_raw
+ * (needed iff p > 0): the softmax itself, SAVED for the backward rather than recomputed.  Dropout element index:
+ * ((n*H + h)*L + i)*L + j.  Backward: dqkv is written whole; dK / dV rows of masked keys are exactly 0. */
+int hmmc_masked_attention_fwd(const float* qkv, const long* key_mask, float* out, float* probs, float* probs_raw, int b, int L,
+                              int H, float p, long seed, int site, hmmc_stream_t stream);
+int hmmc_masked_attention_bwd(const float* qkv, const long* key_mask, const float* probs, const float* probs_raw,
+                              const float* dout, float* dqkv, int b, int L, int H, float p, long seed, int site,
+                              hmmc_stream_t stream);
+/* BertPooler: y[n] = tanh(x[n * stride .. + D] W^T + bias), n < b - the class rows of a [b*L, D] buffer addressed in place
+ * (stride = L*D).  Backward: dz [b, D] (scratch) = dy (1 - y^2); dW, db are written; dx receives dz W at the same class rows
+ * (stride apart) and no other row of dx is touched.  workspace: hmmc_colsum_workspace(b, D) bytes. */
+int hmmc_bert_pooler_fwd(const float* x, const float* W, const float* bias, float* y, int b, long stride, int D,
+                         hmmc_stream_t stream);
+int hmmc_bert_pooler_bwd(const float* dy, const float* y, const float* x, const float* W, float* dz, float* dx, float* dW,
+                         float* db, int b, long stride, int D, void* workspace, size_t ws_bytes, hmmc_stream_t stream);
+/* Tower runtime: BertEmbeddings and all BertLayers in one call each way; y [nseq*L, D] = last_hidden_state.
+ * params / grads: 5 + 16 * nlayers fp32 pointers in the order embeddings.{word_embeddings, position_embeddings,
+ * token_type_embeddings}.weight, embeddings.LayerNorm.{weight, bias}, then per layer attention.self.{query, key, value}.{weight,
+ * bias}, attention.output.dense.{weight, bias}, attention.output.LayerNorm.{weight, bias}, intermediate.dense.{weight, bias},
+ * output.dense.{weight, bias}, output.LayerNorm.{weight, bias}.  The three projections stay separate tensors: three N = D
+ * launches write one [T, 3D] buffer, and no packed copy of them exists.  grads are written, not accumulated.
+ * acts: hmmc_bert_act_bytes(); keep_acts = 0 (no-grad passes) reuses one layer slab.  attn_dropout: p_attn > 0 (the softmax
+ * is then kept beside the dropped probabilities).  Dropout sites: 0 after the embedding LayerNorm; layer i: 1 + 3i on the
+ * probabilities, 2 + 3i after attention.output.dense, 3 + 3i after output.dense.  With p_hidden = 0 the residual adds ride in
+ * the GEMM epilogues and no dropout kernel runs; p_attn = 0 takes the attention kernels without dropout code.
+ * hmmc_bert_bwd takes the SAME p / seed as the forward whose acts it reads, scratch of hmmc_bert_bwd_scratch_bytes() and a
+ * workspace of hmmc_bert_workspace_bytes().  L <= 256, D = 64 * heads <= 1024, D % 8 == 0, inter % 4 == 0. */
+size_t hmmc_bert_act_bytes(int nseq, int L, int heads, int D, int inter, int nlayers, int keep_acts, int attn_dropout);
+size_t hmmc_bert_bwd_scratch_bytes(int nseq, int L, int D, int inter);
+size_t hmmc_bert_workspace_bytes(int nseq, int L, int D, int inter);
+int hmmc_bert_fwd(const long* ids, const long* key_mask, float* y, const void* const* params, void* acts, int keep_acts, int nseq,
+                  int L, int heads, int D, int inter, int nlayers, long vocab, float eps, float p_hidden, float p_attn, long seed,
+                  int* err_flag, hmmc_stream_t stream);
+int hmmc_bert_bwd(const float* dy, const long* ids, const long* key_mask, const void* const* params, void* const* grads,
+                  const void* acts, void* scratch, int nseq, int L, int heads, int D, int inter, int nlayers, long vocab, int max_pos,
+                  int type_vocab, float p_hidden, float p_attn, long seed, void* workspace, size_t ws_bytes, hmmc_stream_t stream);
+
 /* Native layer runtime: all ResidualAttentionBlocks of a tower in one call (modules/module_clip.py:231-268 fp16 CLIP
  * towers, fp32 = 0, eps 1e-5; modules/module_cross.py:114-149 fp32 temporal transformer, fp32 = 1, eps 1e-12).
  * params / grads: nlayers x 12 pointers in the order ln_1.{w,b}, attn.in_proj_{weight,bias}, attn.out_proj.{weight,bias},

@@ -742,30 +742,63 @@ extern "C" int hmmc_gemm_f32(const float* A, const float* B, float* C, int M, in
   return rc;
 }
 
-static int gemm_f32_impl(const float* A, const float* B, float* C, int M, int N, int K, long sam, long sak, long sbk,
-                         long sbn, int ldc, float alpha, const float* bias, const float* resid, float* aux_out,
-                         const float* aux_in, int epilogue, hipStream_t stream) {
+// The decision of hmmc_gemm_f32 for one set of arguments: the argument checks, the 16-byte access flags and the kernel with
+// its operand variants.  The launch path (gemm_f32_impl) and the host-only query (hmmc_gemm_f32_plan) both go through here.
+struct F32Choice { F32Plan plan; int a, b; };                   // a / b: av / bv (small, wave-split-K), amode / bmode (tiled), akc / bkc (DMA)
+
+static int f32_choose(G32& p, F32Choice& ch, const float* A, const float* B, const float* C, const float* aux_out, int M, int N,
+                      int K, long sam, long sak, long sbk, long sbn, int ldc, int num_cu) {
   if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0) return HMMC_ERR_ARG;
   if ((sak != 1 && sam != 1) || (sbk != 1 && sbn != 1)) return HMMC_ERR_UNSUPPORTED;
   long a_ld = sak == 1 ? sam : sak, b_ld = sbk == 1 ? sbn : sbk;
   if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 3) return HMMC_ERR_UNSUPPORTED;
-  if ((epilogue & EPI_BIAS) && !bias) return HMMC_ERR_ARG;
-  if ((epilogue & EPI_RESID) && !resid) return HMMC_ERR_ARG;
-  if ((epilogue & EPI_DGELU) && !aux_in) return HMMC_ERR_ARG;
-  G32 p;
-  p.A = A; p.B = B; p.C = C; p.bias = bias; p.resid = resid; p.aux_out = aux_out; p.aux_in = aux_in;
-  p.M = M; p.N = N; p.K = K; p.sam = sam; p.sak = sak; p.sbk = sbk; p.sbn = sbn; p.ldc = ldc; p.alpha = alpha;
-  p.flags = epilogue;
+  p.A = A; p.B = B; p.C = const_cast<float*>(C); p.aux_out = const_cast<float*>(aux_out);
+  p.M = M; p.N = N; p.K = K; p.sam = sam; p.sak = sak; p.sbk = sbk; p.sbn = sbn; p.ldc = ldc;
   // 16-byte accesses only where the leading dimension and base keep every row aligned
   p.avec = !(a_ld & 3) && !((uintptr_t)A & 15);
   p.bvec = !(b_ld & 3) && !((uintptr_t)B & 15);
   p.cvec = !(ldc & 3) && !((uintptr_t)C & 15) && (!aux_out || !((uintptr_t)aux_out & 15));
-  const F32Plan plan = plan_f32(p, hmmc_num_cus(), hmmc_option(HMMC_OPT_NO_F32_WAVEK), hmmc_option(HMMC_OPT_NO_F32_DMA));
-  // 16-byte k-contiguous operand loads of the wave-split-K and small kernels
-  const bool av = sak == 1 && p.avec && !(K & 3), bv = sbk == 1 && p.bvec && !(K & 3);
+  ch.plan = plan_f32(p, num_cu > 0 ? num_cu : hmmc_num_cus(), hmmc_option(HMMC_OPT_NO_F32_WAVEK), hmmc_option(HMMC_OPT_NO_F32_DMA));
+  switch (ch.plan.kind) {
+    case F32_DMA: ch.a = sak == 1; ch.b = sbk == 1; break;
+    case F32_TILED:
+      ch.a = !p.avec ? OP_SCALAR : sak == 1 ? ((K & 3) ? OP_SCALAR : OP_KVEC) : ((M & 3) ? OP_SCALAR : OP_RVEC);
+      ch.b = !p.bvec ? OP_SCALAR : sbk == 1 ? ((K & 3) ? OP_SCALAR : OP_KVEC) : ((N & 3) ? OP_SCALAR : OP_RVEC);
+      break;
+    default:                                                      // 16-byte k-contiguous operand loads of the wave-split-K and small kernels
+      ch.a = sak == 1 && p.avec && !(K & 3); ch.b = sbk == 1 && p.bvec && !(K & 3);
+      break;
+  }
+  return HMMC_OK;
+}
+
+extern "C" int hmmc_gemm_f32_plan(const float* A, const float* B, const float* C, const float* aux_out, int M, int N, int K,
+                                  long sam, long sak, long sbk, long sbn, int ldc, int num_cu) {
+  G32 p{};
+  F32Choice ch{};
+  const int rc = f32_choose(p, ch, A, B, C, aux_out, M, N, K, sam, sak, sbk, sbn, ldc, num_cu);
+  if (rc != HMMC_OK) return rc;
+  static_assert(F32_SMALL == HMMC_F32_SMALL && F32_TILED == HMMC_F32_TILED && F32_WAVEK == HMMC_F32_WAVEK && F32_DMA == HMMC_F32_DMA,
+                "the header's family codes");
+  return (int)ch.plan.kind | (ch.plan.rm + ch.plan.mi) << 4 | ch.a << 8 | ch.b << 12 | p.cvec << 16;
+}
+
+static int gemm_f32_impl(const float* A, const float* B, float* C, int M, int N, int K, long sam, long sak, long sbk,
+                         long sbn, int ldc, float alpha, const float* bias, const float* resid, float* aux_out,
+                         const float* aux_in, int epilogue, hipStream_t stream) {
+  G32 p;
+  F32Choice ch;
+  const int rc = f32_choose(p, ch, A, B, C, aux_out, M, N, K, sam, sak, sbk, sbn, ldc, 0);
+  if (rc != HMMC_OK) return rc;
+  if ((epilogue & EPI_BIAS) && !bias) return HMMC_ERR_ARG;
+  if ((epilogue & EPI_RESID) && !resid) return HMMC_ERR_ARG;
+  if ((epilogue & EPI_DGELU) && !aux_in) return HMMC_ERR_ARG;
+  p.bias = bias; p.resid = resid; p.aux_in = aux_in; p.alpha = alpha; p.flags = epilogue;
+  const F32Plan plan = ch.plan;
+  const bool av = ch.a, bv = ch.b;
   switch (plan.kind) {
     case F32_DMA: {
-      const bool akc = sak == 1, bkc = sbk == 1;
+      const bool akc = ch.a, bkc = ch.b;
       if (akc && bkc) launch_f32_dma<true, true>(p, plan.mi, stream);
       else if (akc) launch_f32_dma<true, false>(p, plan.mi, stream);
       else if (bkc) launch_f32_dma<false, true>(p, plan.mi, stream);
@@ -786,8 +819,7 @@ static int gemm_f32_impl(const float* A, const float* B, float* C, int M, int N,
       break;
     }
     case F32_TILED: {
-      const int amode = !p.avec ? OP_SCALAR : sak == 1 ? ((K & 3) ? OP_SCALAR : OP_KVEC) : ((M & 3) ? OP_SCALAR : OP_RVEC);
-      const int bmode = !p.bvec ? OP_SCALAR : sbk == 1 ? ((K & 3) ? OP_SCALAR : OP_KVEC) : ((N & 3) ? OP_SCALAR : OP_RVEC);
+      const int amode = ch.a, bmode = ch.b;
       const dim3 grid((unsigned)((long)((M + TM - 1) / TM) * ((N + TN - 1) / TN)));
       switch (amode) {
         case OP_KVEC: launch_f32<OP_KVEC>(bmode, grid, stream, p); break;

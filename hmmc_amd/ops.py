@@ -481,15 +481,20 @@ def attention_f16_bwd_lead(qkv, lse, dout, nseq, L, H, causal, want_dbias=False,
 # ----------------------------------------------------------------------------- fp32 side
 
 
-def gemm_f32(a, b, M, N, K, sa, sb, alpha=1.0, bias=None, resid=None, aux_in=None, epilogue=0, want_aux=False, out=None):
-    """C[M,N] = epi(alpha * sum_k A[m*sa[0] + k*sa[1]] * B[k*sb[0] + n*sb[1]]); a, b are fp32 buffers (any shape)."""
+def gemm_f32(a, b, M, N, K, sa, sb, alpha=1.0, bias=None, resid=None, aux_in=None, epilogue=0, want_aux=False, out=None, ldc=None):
+    """C[M,N] = epi(alpha * sum_k A[m*sa[0] + k*sa[1]] * B[k*sb[0] + n*sb[1]]); a, b are fp32 buffers (any shape).
+    ldc (default N): the row stride of C, aux_out, resid and aux_in; with ldc > N `out` must be given, and out / resid / aux_in may
+    be larger than the (M - 1) ldc + N elements addressed (aux_out then has out's shape and only its addressed elements are written)."""
     _chk(a, torch.float32, "a")
     _chk(b, torch.float32, "b")
     assert (M - 1) * sa[0] + (K - 1) * sa[1] < a.numel(), ("A out of range", M, K, sa, a.shape)
     assert (K - 1) * sb[0] + (N - 1) * sb[1] < b.numel(), ("B out of range", K, N, sb, b.shape)
+    ldc = N if ldc is None else int(ldc)
+    assert ldc >= N and (out is not None or ldc == N), ("ldc", ldc, N)
+    span = (M - 1) * ldc + N
     c = out if out is not None else torch.empty((M, N), dtype=torch.float32, device=a.device)
     _chk(c, torch.float32, "out")
-    assert c.numel() == M * N
+    assert c.numel() >= span if out is not None else c.numel() == M * N
     aux_out = torch.empty_like(c) if want_aux else None
     for t, n in ((bias, "bias"), (resid, "resid"), (aux_in, "aux_in")):
         if t is not None:
@@ -498,11 +503,11 @@ def gemm_f32(a, b, M, N, K, sa, sb, alpha=1.0, bias=None, resid=None, aux_in=Non
         assert bias.numel() == N
         epilogue |= EPI_BIAS
     if resid is not None:
-        assert resid.numel() == M * N
+        assert resid.numel() >= span
         epilogue |= EPI_RESID
     if aux_in is not None:
-        assert aux_in.numel() == M * N
-    call("hmmc_gemm_f32", ptr(a), ptr(b), ptr(c), M, N, K, sa[0], sa[1], sb[0], sb[1], N, float(alpha), ptr(bias),
+        assert aux_in.numel() >= span
+    call("hmmc_gemm_f32", ptr(a), ptr(b), ptr(c), M, N, K, sa[0], sa[1], sb[0], sb[1], ldc, float(alpha), ptr(bias),
          ptr(resid), ptr(aux_out), ptr(aux_in), epilogue)
     return (c, aux_out) if want_aux else c
 

@@ -230,6 +230,27 @@ int hmmc_attention_f16_bwd_lead(const void* qkv, const void* out, const float* l
 int hmmc_gemm_f32(const float* A, const float* B, float* C, int M, int N, int K, long sam, long sak, long sbk, long sbn,
                   int ldc, float alpha, const float* bias, const float* resid, float* aux_out, const float* aux_in,
                   int epilogue, hmmc_stream_t stream);
+/* The decision hmmc_gemm_f32 takes for these arguments, or HMMC_ERR_* as hmmc_gemm_f32 returns it for them (the checks of bias /
+ * resid / aux_in against `epilogue` are not part of the query).  Host only: nothing is launched, no pointer is dereferenced
+ * (A, B, C, aux_out count for their alignment; aux_out may be NULL) and no GPU is needed.  num_cu <= 0: the current device's
+ * compute units; a positive value is used as given.  Honours "no_f32_wavek" / "no_f32_dma".  The value packs
+ *   HMMC_F32_PLAN_FAMILY  HMMC_F32_SMALL (16x32 wave-split), _TILED (64x64 through LDS), _WAVEK ((16 rm) x 64 wave-split-K), _DMA ((32 mi) x 64 LDS-DMA)
+ *   HMMC_F32_PLAN_TILE    rm in {2, 3, 4, 6} (WAVEK), mi in {1, 2} (DMA), 0 otherwise
+ *   HMMC_F32_PLAN_A / _B  the operand variant instantiated: SMALL, WAVEK 1 = 16-byte k-contiguous loads, 0 = 4-byte loads;
+ *                         TILED 0 = 16-byte loads along k, 1 = 16-byte loads along the rows, 2 = 4-byte loads;
+ *                         DMA 1 = k-contiguous, 0 = row-contiguous
+ *   HMMC_F32_PLAN_CVEC    1 = 16-byte stores of C / aux_out, 0 = 4-byte stores */
+#define HMMC_F32_SMALL 0
+#define HMMC_F32_TILED 1
+#define HMMC_F32_WAVEK 2
+#define HMMC_F32_DMA 3
+#define HMMC_F32_PLAN_FAMILY(plan) ((plan) & 15)
+#define HMMC_F32_PLAN_TILE(plan) (((plan) >> 4) & 15)
+#define HMMC_F32_PLAN_A(plan) (((plan) >> 8) & 15)
+#define HMMC_F32_PLAN_B(plan) (((plan) >> 12) & 15)
+#define HMMC_F32_PLAN_CVEC(plan) (((plan) >> 16) & 1)
+int hmmc_gemm_f32_plan(const float* A, const float* B, const float* C, const float* aux_out, int M, int N, int K, long sam,
+                       long sak, long sbk, long sbn, int ldc, int num_cu);
 
 /* y = x / max(||x||, eps) per row (eps 0: loose_similarity, modules/modeling.py:210-214; eps 1e-12: F.normalize, :289-292). */
 int hmmc_l2norm_fwd(const float* x, float* y, float* norm, int rows, int D, float eps, hmmc_stream_t stream);

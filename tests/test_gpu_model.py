@@ -69,8 +69,10 @@ def test_gemm_f32_all_orientations():
 @pytest.mark.parametrize("M,N,K", [(3072, 512, 2048), (1536, 512, 2048), (2048, 512, 1536), (700, 512, 4096), (1000, 500, 2052),
                                    (333, 260, 3001)])
 def test_gemm_f32_long_k_single_round_exact_integers(M, N, K):
-    """Shapes the fp32 dispatcher gives to the wave-split-K kernel (at most one (16 RM) x 64 tile per CU, long K; tile heights
-    96 / 48 / 64 / 32, ragged edges, K % 4 != 0 = the scalar-load variants), in the three operand orientations of the path
+    """Long-K shapes of the fp32 path.  By hmmc_gemm_f32_plan on a 256-CU part the 2nd to 5th take the wave-split-K kernel (tile
+    heights 48 / 64 / 32 / 32), the first the LDS-DMA kernel's 32 x 64 tiles and the last (K % 4 != 0) the 16 x 32 kernel's
+    scalar-load variant; tests/test_gpu_gemm_f32.py asserts the plan of every instantiation it runs, the 96-row tiles included.
+    In the three operand orientations of the path
     (x W^T, dy W, dy^T x; reference modules/module_cross.py:114-149).  Integer-valued operands: every product and partial
     sum is exact in fp32, so the result must EQUAL the fp64 product whatever the order of the four waves' partial tiles."""
     g = torch.Generator().manual_seed(M + N + K)

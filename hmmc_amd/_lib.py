@@ -22,10 +22,12 @@ _CODE = {"int": "i", "long": "l", "float": "f", "size_t": "z"}
 
 def _parse_header(path=HEADER):
     """include/hmmc_hip.h -> (SIGNATURES: name -> (argument codes, return code) of every entry point, ERRORS: HMMC_ERR_* value ->
-    the message in its comment, EPI: "EPI_<flag>" -> the value of HMMC_EPI_<flag>).  Argument codes are keys of _C: "p" any
-    pointer (hmmc_stream_t included), "s" const char*."""
+    the message in its comment, EPI: "EPI_<flag>" -> the value of HMMC_EPI_<flag>, STATUS: "HMMC_ERR_<name>" -> its value).
+    Argument codes are keys of _C: "p" any pointer (hmmc_stream_t included), "s" const char*."""
     src = open(path).read()
-    errors = {int(v): msg for v, msg in re.findall(r"#define HMMC_ERR_\w+ \((-\d+)\)\s*/\*\s*(.*?)\s*\*/", src)}
+    defs = re.findall(r"#define (HMMC_ERR_\w+) \((-\d+)\)\s*/\*\s*(.*?)\s*\*/", src)
+    errors = {int(v): msg for _, v, msg in defs}
+    status = {name: int(v) for name, v, _ in defs}
     epi = {"EPI_" + name: int(v) for name, v in re.findall(r"#define HMMC_EPI_(\w+) (\d+)", src)}
     sigs = {}
     for ret, name, args in re.findall(r"\b(int|size_t)\s+(hmmc_\w+)\s*\(([^;]*?)\)\s*;", re.sub(r"/\*.*?\*/", "", src, flags=re.S)):
@@ -38,10 +40,10 @@ def _parse_header(path=HEADER):
             else:
                 codes += _CODE[a.split()[-2] if len(a.split()) > 1 else a]
         sigs[name] = (codes, _CODE[ret])
-    return sigs, errors, epi
+    return sigs, errors, epi, status
 
 
-SIGNATURES, ERRORS, EPI = _parse_header()
+SIGNATURES, ERRORS, EPI, STATUS = _parse_header()
 
 # The library reads no environment variable itself (include/hmmc_hip.h: hmmc_set_option).  These A/B switches of scratch/ runs
 # and tests are translated once, when the library is loaded; a variable that is PRESENT (any value, the empty string included)
@@ -94,6 +96,15 @@ def ptr(t):
 
 def stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def call_status(name, *args, allow=None):
+    """Call an int-returning entry point on the current stream -> its status: 0, or the HMMC_ERR_* named `allow` (the caller has
+    another way); raise on any other."""
+    rc = getattr(load(), name)(*args, stream())
+    if rc != 0 and (allow is None or rc != STATUS[allow]):
+        raise RuntimeError(f"{name} failed: {ERRORS.get(rc, rc)}")
+    return rc
 
 
 def call(name, *args):

@@ -539,11 +539,9 @@ static void launch_long_bwd2(const AttnArgs& p, hipStream_t stream) {
   constexpr int LDS = 4 * 16 * KTL * DH * 2 + NW * 16 * LDS_STRIDE * 2 + 2 * 16 * KTL * 4   // K, V, Q, dO images + staging per wave + lse, delta
                       + 3 * NW * 64 * 4 + 16 * KTL * 4;                                  // + the waves' column sums + the row factors
   static_assert(LDS <= 160 * 1024, "LDS budget");
-  static bool done[HMMC_MAX_DEVICES] = {false};
-  hmmc_allow_lds((const void*)attn_long_bwd_kernel<KTL, NW, CAUSAL, LEAD>, LDS, done);
   const long total = (long)p.nseq * p.H;
   const long wgs = hmmc_num_cus();                                         // persistent: one workgroup per CU
-  hipLaunchKernelGGL((attn_long_bwd_kernel<KTL, NW, CAUSAL, LEAD>), dim3((unsigned)(total < wgs ? total : wgs)), dim3(64 * NW), LDS, stream, p);
+  hmmc_launch_lds<attn_long_bwd_kernel<KTL, NW, CAUSAL, LEAD>>(LDS, dim3((unsigned)(total < wgs ? total : wgs)), dim3(64 * NW), LDS, stream, p);
 }
 template <int KTL, int NW>
 static void launch_long_bwd(const AttnArgs& p, hipStream_t stream, bool lead) {

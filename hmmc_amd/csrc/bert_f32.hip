@@ -10,16 +10,6 @@
 
 namespace {
 
-inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
-#define CK(call) do { int rc_ = (call); if (rc_ != 0) return rc_; } while (0)
-#define HIPCK(call) do { if ((call) != hipSuccess) return HMMC_ERR_LAUNCH; } while (0)
-
-inline int nblk(long work, int cap = 4096) {
-  long b = (work + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
 // ---------------------------------------------------------------- dropout: Philox4x32-10 (Salmon et al., SC'11)
 // The keep decision of element `idx` of dropout site `site` is word (idx & 3) of Philox(key = seed, counter = (idx >> 2, site)):
 // a pure function of (seed, site, idx), so the backward regenerates it and no mask is stored.
@@ -508,27 +498,16 @@ extern "C" int hmmc_masked_attention_fwd(const float* qkv, const long* key_mask,
   if (p > 0.f && !probs_raw) return HMMC_ERR_ARG;
   if (L > MA_MAXL) return HMMC_ERR_UNSUPPORTED;
   const Drop dr = make_drop(p, seed, site);
+  const dim3 grid(b * H);
   if (L > 64) {
     const size_t lds = (size_t)(2 * L * 65 + 4 * MA_MAXL + 4 * 64 + MA_MAXL) * sizeof(float);
-    static bool done0[HMMC_MAX_DEVICES] = {false}, done1[HMMC_MAX_DEVICES] = {false};
-    if (p > 0.f) {
-      hmmc_allow_lds((const void*)mattn_long_fwd_kernel<true>, 160 * 1024 - 4096, done1);
-      hipLaunchKernelGGL(mattn_long_fwd_kernel<true>, dim3(b * H), dim3(256), lds, stream, qkv, key_mask, out, probs, probs_raw, L, H, dr);
-    } else {
-      hmmc_allow_lds((const void*)mattn_long_fwd_kernel<false>, 160 * 1024 - 4096, done0);
-      hipLaunchKernelGGL(mattn_long_fwd_kernel<false>, dim3(b * H), dim3(256), lds, stream, qkv, key_mask, out, probs, probs_raw, L, H, dr);
-    }
+    if (p > 0.f) hmmc_launch_lds<mattn_long_fwd_kernel<true>>(HMMC_LDS_MOST, grid, dim3(256), lds, stream, qkv, key_mask, out, probs, probs_raw, L, H, dr);
+    else hmmc_launch_lds<mattn_long_fwd_kernel<false>>(HMMC_LDS_MOST, grid, dim3(256), lds, stream, qkv, key_mask, out, probs, probs_raw, L, H, dr);
     return hmmc_launch_status();
   }
   const size_t lds = (size_t)(3 * L * 65 + L * L + L) * sizeof(float);
-  static bool done0[HMMC_MAX_DEVICES] = {false}, done1[HMMC_MAX_DEVICES] = {false};
-  if (p > 0.f) {
-    hmmc_allow_lds((const void*)mattn_fwd_kernel<true>, 160 * 1024 - 4096, done1);
-    hipLaunchKernelGGL(mattn_fwd_kernel<true>, dim3(b * H), dim3(64), lds, stream, qkv, key_mask, out, probs, probs_raw, L, H, dr);
-  } else {
-    hmmc_allow_lds((const void*)mattn_fwd_kernel<false>, 160 * 1024 - 4096, done0);
-    hipLaunchKernelGGL(mattn_fwd_kernel<false>, dim3(b * H), dim3(64), lds, stream, qkv, key_mask, out, probs, probs_raw, L, H, dr);
-  }
+  if (p > 0.f) hmmc_launch_lds<mattn_fwd_kernel<true>>(HMMC_LDS_MOST, grid, dim3(64), lds, stream, qkv, key_mask, out, probs, probs_raw, L, H, dr);
+  else hmmc_launch_lds<mattn_fwd_kernel<false>>(HMMC_LDS_MOST, grid, dim3(64), lds, stream, qkv, key_mask, out, probs, probs_raw, L, H, dr);
   return hmmc_launch_status();
 }
 
@@ -539,28 +518,16 @@ extern "C" int hmmc_masked_attention_bwd(const float* qkv, const long* key_mask,
   if (p > 0.f && !probs_raw) return HMMC_ERR_ARG;
   if (L > MA_MAXL) return HMMC_ERR_UNSUPPORTED;
   const Drop dr = make_drop(p, seed, site);
+  const dim3 grid(b * H);
   if (L > 64) {
     const size_t lds = (size_t)(2 * L * 65 + 4 * MA_MAXL + MA_MAXL + MA_MAXL) * sizeof(float);
-    static bool done0[HMMC_MAX_DEVICES] = {false}, done1[HMMC_MAX_DEVICES] = {false};
-    if (p > 0.f) {
-      hmmc_allow_lds((const void*)mattn_long_bwd_kernel<true>, 160 * 1024 - 4096, done1);
-      hipLaunchKernelGGL(mattn_long_bwd_kernel<true>, dim3(b * H), dim3(256), lds, stream, qkv, key_mask, probs, probs_raw, dout, dqkv, L, H, dr);
-    } else {
-      hmmc_allow_lds((const void*)mattn_long_bwd_kernel<false>, 160 * 1024 - 4096, done0);
-      hipLaunchKernelGGL(mattn_long_bwd_kernel<false>, dim3(b * H), dim3(256), lds, stream, qkv, key_mask, probs, probs_raw, dout, dqkv, L, H, dr);
-    }
+    if (p > 0.f) hmmc_launch_lds<mattn_long_bwd_kernel<true>>(HMMC_LDS_MOST, grid, dim3(256), lds, stream, qkv, key_mask, probs, probs_raw, dout, dqkv, L, H, dr);
+    else hmmc_launch_lds<mattn_long_bwd_kernel<false>>(HMMC_LDS_MOST, grid, dim3(256), lds, stream, qkv, key_mask, probs, probs_raw, dout, dqkv, L, H, dr);
     return hmmc_launch_status();
   }
-  static bool done0[HMMC_MAX_DEVICES] = {false}, done1[HMMC_MAX_DEVICES] = {false};
-  if (p > 0.f) {
-    const size_t lds = (size_t)(4 * L * 65 + 3 * L * L + L) * sizeof(float);
-    hmmc_allow_lds((const void*)mattn_bwd_kernel<true>, 160 * 1024 - 4096, done1);
-    hipLaunchKernelGGL(mattn_bwd_kernel<true>, dim3(b * H), dim3(64), lds, stream, qkv, key_mask, probs, probs_raw, dout, dqkv, L, H, dr);
-  } else {
-    const size_t lds = (size_t)(4 * L * 65 + 2 * L * L + L) * sizeof(float);
-    hmmc_allow_lds((const void*)mattn_bwd_kernel<false>, 160 * 1024 - 4096, done0);
-    hipLaunchKernelGGL(mattn_bwd_kernel<false>, dim3(b * H), dim3(64), lds, stream, qkv, key_mask, probs, probs_raw, dout, dqkv, L, H, dr);
-  }
+  const size_t lds = (size_t)(4 * L * 65 + (p > 0.f ? 3 : 2) * L * L + L) * sizeof(float);
+  if (p > 0.f) hmmc_launch_lds<mattn_bwd_kernel<true>>(HMMC_LDS_MOST, grid, dim3(64), lds, stream, qkv, key_mask, probs, probs_raw, dout, dqkv, L, H, dr);
+  else hmmc_launch_lds<mattn_bwd_kernel<false>>(HMMC_LDS_MOST, grid, dim3(64), lds, stream, qkv, key_mask, probs, probs_raw, dout, dqkv, L, H, dr);
   return hmmc_launch_status();
 }
 

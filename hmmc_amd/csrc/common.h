@@ -41,6 +41,29 @@ static inline void hmmc_allow_lds(const void* kernel, int bytes, bool (&done)[HM
   (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   done[dev] = true;
 }
+constexpr int HMMC_LDS_MOST = 160 * 1024 - 4096;   // what the fp32 attention kernels opt in to: the CU's 160 KiB less 4 KiB
+// The opt-in and the launch in one: every kernel (the template argument) owns its per-device flags, whatever the argument types
+// of a call site.  `allow`: the dynamic LDS the kernel may ask for in any launch; `lds`: what this launch asks for.
+template <auto Kernel>
+static inline void hmmc_allow_lds_once(int bytes) {
+  static bool done[HMMC_MAX_DEVICES] = {false};
+  hmmc_allow_lds((const void*)Kernel, bytes, done);
+}
+template <auto Kernel, typename... Args>
+static inline void hmmc_launch_lds(int allow, dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args) {
+  hmmc_allow_lds_once<Kernel>(allow);
+  hipLaunchKernelGGL(Kernel, grid, block, lds, stream, args...);
+}
+
+// host helpers of the files that sequence kernels: 256-byte carving of a caller-owned buffer, early return on an HMMC_ERR_* or
+// a HIP error, 256-thread blocks for `work` items
+static inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
+static inline int nblk(long work, int cap = 4096) {
+  long b = (work + 255) / 256;
+  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+#define CK(call) do { int rc_ = (call); if (rc_ != 0) return rc_; } while (0)
+#define HIPCK(call) do { if ((call) != hipSuccess) return HMMC_ERR_LAUNCH; } while (0)
 
 // compute units of the current device (queried once per device)
 static inline int hmmc_num_cus() {

@@ -422,11 +422,6 @@ __global__ __launch_bounds__(256) void gattn_bwd_kernel(const float* __restrict_
   }
 }
 
-inline int nblk(long work, int cap = 4096) {
-  long b = (work + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
 }  // namespace
 
 extern "C" int hmmc_l2norm_fwd(const float* x, float* y, float* norm, int rows, int D, float eps, hipStream_t stream) {
@@ -544,15 +539,11 @@ extern "C" int hmmc_temporal_attention_fwd(const float* qkv, float* out, float* 
   if (F > GA_MAXL) return HMMC_ERR_UNSUPPORTED;
   if (F > 64) {                                  // the CLIP towers' token counts in the fp32 regime (parity path)
     size_t gl = (size_t)(2 * F * 65 + 4 * GA_MAXL + 4 * 64) * sizeof(float);
-    static bool gdone[HMMC_MAX_DEVICES] = {false};
-    hmmc_allow_lds((const void*)gattn_fwd_kernel, 160 * 1024 - 4096, gdone);
-    hipLaunchKernelGGL(gattn_fwd_kernel, dim3(b * H), dim3(256), gl, stream, qkv, out, probs, F, H, causal);
+    hmmc_launch_lds<gattn_fwd_kernel>(HMMC_LDS_MOST, dim3(b * H), dim3(256), gl, stream, qkv, out, probs, F, H, causal);
     return hmmc_launch_status();
   }
   size_t lds = (size_t)(3 * F * 65 + F * F) * sizeof(float);
-  static bool done[HMMC_MAX_DEVICES] = {false};
-  hmmc_allow_lds((const void*)tattn_fwd_kernel, 160 * 1024 - 4096, done);
-  hipLaunchKernelGGL(tattn_fwd_kernel, dim3(b * H), dim3(64), lds, stream, qkv, out, probs, F, H, causal);
+  hmmc_launch_lds<tattn_fwd_kernel>(HMMC_LDS_MOST, dim3(b * H), dim3(64), lds, stream, qkv, out, probs, F, H, causal);
   return hmmc_launch_status();
 }
 
@@ -562,14 +553,10 @@ extern "C" int hmmc_temporal_attention_bwd(const float* qkv, const float* probs,
   if (F > GA_MAXL) return HMMC_ERR_UNSUPPORTED;
   if (F > 64) {
     size_t gl = (size_t)(2 * F * 65 + 4 * GA_MAXL + GA_MAXL) * sizeof(float);
-    static bool gdone[HMMC_MAX_DEVICES] = {false};
-    hmmc_allow_lds((const void*)gattn_bwd_kernel, 160 * 1024 - 4096, gdone);
-    hipLaunchKernelGGL(gattn_bwd_kernel, dim3(b * H), dim3(256), gl, stream, qkv, probs, dout, dqkv, F, H);
+    hmmc_launch_lds<gattn_bwd_kernel>(HMMC_LDS_MOST, dim3(b * H), dim3(256), gl, stream, qkv, probs, dout, dqkv, F, H);
     return hmmc_launch_status();
   }
   size_t lds = (size_t)(4 * F * 65 + 2 * F * F) * sizeof(float);
-  static bool done[HMMC_MAX_DEVICES] = {false};
-  hmmc_allow_lds((const void*)tattn_bwd_kernel, 160 * 1024 - 4096, done);
-  hipLaunchKernelGGL(tattn_bwd_kernel, dim3(b * H), dim3(64), lds, stream, qkv, probs, dout, dqkv, F, H);
+  hmmc_launch_lds<tattn_bwd_kernel>(HMMC_LDS_MOST, dim3(b * H), dim3(64), lds, stream, qkv, probs, dout, dqkv, F, H);
   return hmmc_launch_status();
 }

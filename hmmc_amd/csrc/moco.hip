@@ -10,11 +10,6 @@
 
 namespace {
 
-inline int nblk(long work, int cap = 4096) {
-  long b = (work + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
 // ---------------------------------------------------------------- BatchNorm1d over rows
 // partial[slab][0|1][N]: per-slab column sum and sum of squares; 32 columns x 8 row lanes per block
 __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const float* __restrict__ h, float* __restrict__ partial,

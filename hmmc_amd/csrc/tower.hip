@@ -19,8 +19,6 @@
 
 namespace {
 
-inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // activation slab of one layer (es = element size: 2 fp16 tower, 4 fp32 tower)
 struct Acts {
   char *x, *ln1, *qkv, *att, *x1, *ln2, *h, *g;
@@ -83,8 +81,6 @@ inline int wgrad(bool f32, const void* dy, const void* x, void* dw, int T, int N
   return hmmc_gemm_f16(dy, x, dw, Np, Kp, T, ldy ? ldy : Np, ldx ? ldx : Kp, Kp, 0, 0, nullptr, nullptr, nullptr, nullptr, 0,
                        need <= wsb ? ws : nullptr, need <= wsb ? wsb : 0, s);
 }
-
-#define CK(call) do { int rc_ = (call); if (rc_ != 0) return rc_; } while (0)
 
 // The attention half of a LAST block whose caller reads the class token alone (lead_only), sequences of at most 256 tokens: only
 // query 0 of every sequence is wanted, so K | V are projected for every token, Q for the nseq class tokens only (their rows of
@@ -277,6 +273,14 @@ extern "C" size_t hmmc_tower_fold_bytes(long tokens, int D, int nlayers, int tra
   return fold_carve(nullptr, tokens, D, nlayers, train, nullptr).bytes;
 }
 
+// The shapes hmmc_tower_fwd_fused takes (no device state is read): operands below 2 GiB (32-bit offsets, as hmmc_tower_fwd's
+// GEMMs); train (keep_acts = 1, hmmc_tower_bwd_fold): also the short-sequence attention and the grouped weight-gradient launch,
+// which the folded weight gradients need - D % 256 == 0, >= 512 tokens, the "no_wgrad_group" option off.
+extern "C" int hmmc_tower_fold_supported(long tokens, int D, int L, int train) {
+  if ((uint64_t)(tokens + 256) * 4 * D * 2 >= (1ull << 31) - (1ull << 24)) return 0;
+  return !train || (L <= 256 && group_ws_bytes(tokens, D) > 0);
+}
+
 // y = tower(x) for an fp16 tower with ln_1 / ln_2 folded into in_proj / c_fc: the same blocks as hmmc_tower_fwd
 // (modules/module_clip.py:231-257) without the four LayerNorm passes over the residual stream per layer.
 // keep_acts = 0 (eval, momentum encoders): acts is ONE slab of hmmc_tower_act_bytes(), fold_ws = hmmc_tower_fold_bytes(.., 0).
@@ -290,9 +294,8 @@ extern "C" int hmmc_tower_fwd_fused(const void* x, const float* x_stat, void* y,
                                     void* fold_ws, size_t fold_bytes, hipStream_t s) {
   if (!x || !y || !params || !acts || !fold_ws || nseq <= 0 || L <= 0 || heads <= 0 || nlayers <= 0 || D != heads * 64) return HMMC_ERR_ARG;
   const long T = (long)nseq * L;
-  if ((uint64_t)(T + 256) * 4 * D * 2 >= (1ull << 31) - (1ull << 24)) return HMMC_ERR_UNSUPPORTED;     // operands of 2 GiB: hmmc_tower_fwd
-  // training: the folded weight gradients exist for the grouped launch, and a lead-only last layer must be the unfolded one
-  if (keep_acts && (L > 256 || group_ws_bytes(T, D) == 0 || (lead_only && !last_exact))) return HMMC_ERR_UNSUPPORTED;
+  // a shape for hmmc_tower_fwd; training: a lead-only last layer must be the unfolded one
+  if (!hmmc_tower_fold_supported(T, D, L, keep_acts) || (keep_acts && lead_only && !last_exact)) return HMMC_ERR_UNSUPPORTED;
   const int nfold = nfold_of(nlayers, last_exact);
   std::vector<FoldLayer> fl(nlayers);
   const FoldWs fw = fold_carve((char*)fold_ws, T, D, nlayers, keep_acts, fl.data());
@@ -330,7 +333,7 @@ extern "C" int hmmc_tower_fwd_fused(const void* x, const float* x_stat, void* y,
     const float* st_in = stat1;
     if (i == 0) {
       if (x_stat && !keep_acts) st_in = x_stat;
-      else if (x_stat) { if (hipMemcpyAsync(stat1, x_stat, (size_t)T * 8, hipMemcpyDeviceToDevice, s) != hipSuccess) return HMMC_ERR_LAUNCH; }
+      else if (x_stat) HIPCK(hipMemcpyAsync(stat1, x_stat, (size_t)T * 8, hipMemcpyDeviceToDevice, s));
       else CK(hmmc_rowstat(x, stat1, (int)T, D, D, eps, s));
     }
     if (!lead_attention(lead, false, L)) {
@@ -347,12 +350,11 @@ extern "C" int hmmc_tower_fwd_fused(const void* x, const float* x_stat, void* y,
       float* const st_q = cd_q + 2 * D;                   // [nseq][2]
       const size_t fb = sizeof(float);
       if ((size_t)(6 * D + 2 * nseq) > (size_t)nparts * T * 2) return HMMC_ERR_WORKSPACE;
-      if (hipMemcpyAsync(cd_kv, fl[i].cd1 + D, 2 * D * fb, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-          hipMemcpyAsync(cd_kv + 2 * D, fl[i].cd1 + 3 * D + D, 2 * D * fb, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-          hipMemcpyAsync(cd_q, fl[i].cd1, D * fb, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-          hipMemcpyAsync(cd_q + D, fl[i].cd1 + 3 * D, D * fb, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-          hipMemcpy2DAsync(st_q, 2 * fb, st_in, (size_t)L * 2 * fb, 2 * fb, nseq, hipMemcpyDeviceToDevice, s) != hipSuccess)
-        return HMMC_ERR_LAUNCH;
+      HIPCK(hipMemcpyAsync(cd_kv, fl[i].cd1 + D, 2 * D * fb, hipMemcpyDeviceToDevice, s));
+      HIPCK(hipMemcpyAsync(cd_kv + 2 * D, fl[i].cd1 + 3 * D + D, 2 * D * fb, hipMemcpyDeviceToDevice, s));
+      HIPCK(hipMemcpyAsync(cd_q, fl[i].cd1, D * fb, hipMemcpyDeviceToDevice, s));
+      HIPCK(hipMemcpyAsync(cd_q + D, fl[i].cd1 + 3 * D, D * fb, hipMemcpyDeviceToDevice, s));
+      HIPCK(hipMemcpy2DAsync(st_q, 2 * fb, st_in, (size_t)L * 2 * fb, 2 * fb, nseq, hipMemcpyDeviceToDevice, s));
       const half_t* const w1 = (const half_t*)fl[i].w1;
       CK(hmmc_gemm_f16_fold(xin, w1 + (size_t)D * D, (half_t*)a.qkv + D, (int)T, 2 * D, D, D, D, 3 * D, 1, nullptr, nullptr, nullptr, nullptr,
                             EPI_LNFOLD, st_in, cd_kv, nullptr, nullptr, 0, s));
@@ -485,14 +487,14 @@ extern "C" int hmmc_tower_bwd(const void* dy, void* dx, const void* x0, const vo
 // epilogue HMMC_EPI_ROWSCALE, hmmc_attention_f16_bwd_scaled), the data gradients go through the folded weights, the
 // LayerNorm backward needs no gamma (hmmc_layernorm_bwd_fold), the in_proj / c_fc weight gradients are taken against the raw
 // residual stream into fp32 and finished - together with dgamma / dbeta of ln_1 / ln_2 - by ONE hmmc_fold_grad_finish at the
-// end (ln_fold.hip has the algebra).  Needs the grouped weight-gradient path (D % 256 == 0, >= 2048 tokens).
+// end (ln_fold.hip has the algebra).  Shapes: hmmc_tower_fold_supported(.., train = 1).
 extern "C" int hmmc_tower_bwd_fold(const void* dy, void* dx, const void* x0, const void* const* params, void* const* grads,
                                    const void* acts, void* fold_ws, size_t fold_bytes, void* scratch, int nseq, int L, int heads, int D,
                                    int nlayers, int causal, int lead_only, int last_exact, void* workspace, size_t ws_bytes,
                                    hipStream_t wgrad_stream, hipStream_t s) {
   if (!fold_ws || nseq <= 0 || L <= 0 || nlayers <= 0) return HMMC_ERR_ARG;
   const long T = (long)nseq * L;
-  if (L > 256 || group_ws_bytes(T, D) == 0 || (lead_only && !last_exact)) return HMMC_ERR_UNSUPPORTED;
+  if (!hmmc_tower_fold_supported(T, D, L, 1) || (lead_only && !last_exact)) return HMMC_ERR_UNSUPPORTED;
   std::vector<FoldLayer> fl(nlayers);
   const FoldWs fw = fold_carve((char*)fold_ws, T, D, nlayers, 1, fl.data());
   if (fold_bytes < fw.bytes) return HMMC_ERR_WORKSPACE;
@@ -567,25 +569,23 @@ static int tower_bwd_impl(const void* dy, void* dx, const void* x0, const void* 
   // weight gradient k of a layer (0: c_proj <- g_in, 1: c_fc <- dh, 2: out_proj <- dx1, 3: in_proj <- dqkv)
   auto side_wgrad = [&](int k, const void* dyk, const void* xk, void* dW, int Np, int Kp, int rows = 0, int ldy = 0,
                         int ldx = 0) -> int {
-    if (two) {
-      if (hipEventRecord(syncp->ready, s) != hipSuccess || hipStreamWaitEvent(sw, syncp->ready, 0) != hipSuccess) return HMMC_ERR_LAUNCH;
-    }
+    if (two) { HIPCK(hipEventRecord(syncp->ready, s)); HIPCK(hipStreamWaitEvent(sw, syncp->ready, 0)); }
     int rc = wgrad(f32, dyk, xk, dW, rows ? rows : (int)T, Np, Kp, two ? wws : workspace, two ? wws_bytes : gen, sw, ldy, ldx);
     if (rc == 0 && two) {
-      if (hipEventRecord(syncp->done[k], sw) != hipSuccess) return HMMC_ERR_LAUNCH;
+      HIPCK(hipEventRecord(syncp->done[k], sw));
       done_set[k] = true;
     }
     return rc;
   };
   // the chain on `s` is about to overwrite the operand weight gradient k read (scratch buffers are reused every layer)
   auto before_overwrite = [&](int k) -> int {
-    if (two && done_set[k] && hipStreamWaitEvent(s, syncp->done[k], 0) != hipSuccess) return HMMC_ERR_LAUNCH;
+    if (two && done_set[k]) HIPCK(hipStreamWaitEvent(s, syncp->done[k], 0));
     return 0;
   };
   // `s` waits for the grouped launch that read operand set k: the chain is about to overwrite it
   auto wait_group = [&](int k) -> int {
     if (two && gdone_set[k]) {
-      if (hipStreamWaitEvent(s, syncp->gdone[k], 0) != hipSuccess) return HMMC_ERR_LAUNCH;
+      HIPCK(hipStreamWaitEvent(s, syncp->gdone[k], 0));
       gdone_set[k] = false;
     }
     return 0;
@@ -621,7 +621,7 @@ static int tower_bwd_impl(const void* dy, void* dx, const void* x0, const void* 
     const bool group_layer = grouped && !lead;
     CK(wait_group(par));
     // ---- MLP, x2 = x1 + c_proj(QuickGELU(c_fc(ln2))): dh, dx1 and datt (in dln)
-    if (lead && hipMemsetAsync(dx1, 0, (size_t)T * D * es, s) != hipSuccess) return HMMC_ERR_LAUNCH;
+    if (lead) HIPCK(hipMemsetAsync(dx1, 0, (size_t)T * D * es, s));
     if (!group_layer) CK(side_wgrad(0, g_in, a.g, G[10], D, 4 * D, R, ldr, 0));
     CK(before_overwrite(1));
     if (f32) {
@@ -644,7 +644,7 @@ static int tower_bwd_impl(const void* dy, void* dx, const void* x0, const void* 
     if (!group_layer) CK(side_wgrad(2, dx1, a.att, G[4], D, D, R, ldr, ldr));
     // the attention of a lead_attention() block reads datt on the leading rows alone
     const bool lead_attn = lead_attention(lead, f32, L);
-    if (lead && !lead_attn && hipMemsetAsync(dln, 0, (size_t)T * D * es, s) != hipSuccess) return HMMC_ERR_LAUNCH;
+    if (lead && !lead_attn) HIPCK(hipMemsetAsync(dln, 0, (size_t)T * D * es, s));
     CK(dgrad(f32, dx1, P[4], dln, R, D, D, nullptr, 0, s, ldr, ldr));                    // datt
     // ---- attention, x1 = x + out_proj(attn(in_proj(ln1))): dqkv, the layer's remaining weight gradients and dln = d(ln1)
     CK(before_overwrite(3));
@@ -679,10 +679,10 @@ static int tower_bwd_impl(const void* dy, void* dx, const void* x0, const void* 
         float* gw32[4] = {nullptr, f ? f->s2 : nullptr, nullptr, f ? f->s1 : nullptr};
         int Np[4], Kp[4];
         group_dims(D, Np, Kp);
-        if (two && (hipEventRecord(syncp->ready, s) != hipSuccess || hipStreamWaitEvent(sw, syncp->ready, 0) != hipSuccess)) return HMMC_ERR_LAUNCH;
+        if (two) { HIPCK(hipEventRecord(syncp->ready, s)); HIPCK(hipStreamWaitEvent(sw, syncp->ready, 0)); }
         CK(hmmc_gemm_f16_wgrad_group(gy, gx, gw, f ? gw32 : nullptr, Np, Kp, 4, (int)T, two ? wws : workspace, two ? wws_bytes : gen, sw));
         if (two) {
-          if (hipEventRecord(syncp->gdone[par], sw) != hipSuccess) return HMMC_ERR_LAUNCH;
+          HIPCK(hipEventRecord(syncp->gdone[par], sw));
           gdone_set[par] = true;
         }
       } else {
@@ -700,9 +700,7 @@ static int tower_bwd_impl(const void* dy, void* dx, const void* x0, const void* 
     g_in = g_out;
   }
   if (!tasks.empty()) CK(hmmc_multi_colreduce(tasks.data(), (int)tasks.size(), s));
-  if (two) {                                     // hand the weight gradients back in `s` order
-    if (hipEventRecord(syncp->ready, sw) != hipSuccess || hipStreamWaitEvent(s, syncp->ready, 0) != hipSuccess) return HMMC_ERR_LAUNCH;
-  }
+  if (two) { HIPCK(hipEventRecord(syncp->ready, sw)); HIPCK(hipStreamWaitEvent(s, syncp->ready, 0)); }     // hand the weight gradients back in `s` order
   if (fb && fb->nfold > 0) {
     // the folded layers' in_proj / c_fc weight gradients and ln_1 / ln_2 gradients from the fp32 sums against the raw rows: they
     // need the bias gradients the reduce above just wrote and the sums the weight-gradient stream just handed back

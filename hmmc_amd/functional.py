@@ -134,7 +134,7 @@ def vit_embed(video4d, conv_w, cls, pos, ln_w, ln_b, frame_index=None):
     if conv_w.dtype != torch.float16:
         return VitEmbedFn.apply(video4d, conv_w, cls, pos, ln_w, ln_b, frame_index), None
     if torch.is_grad_enabled() and any(t.requires_grad for t in (conv_w, cls, pos, ln_w, ln_b)):
-        if _FOLD_LN_TRAIN in ("0", "", "off", False):
+        if _fold_off(_FOLD_LN_TRAIN):                      # no tower folds in training: nobody reads the row pairs
             return VitEmbedFn.apply(video4d, conv_w, cls, pos, ln_w, ln_b, frame_index), None
         return VitEmbedFn.apply(video4d, conv_w, cls, pos, ln_w, ln_b, frame_index, True)      # (x, row pairs of x)
     D, _, p, _ = conv_w.shape
@@ -186,63 +186,70 @@ _FOLD_LN = os.environ.get("HMMC_FOLD_LN", "vit")
 # unfolded kernels.  HMMC_FOLD_LN_TRAIN: "vit" (default), "all", "0".
 _FOLD_LN_TRAIN = os.environ.get("HMMC_FOLD_LN_TRAIN", "vit")
 
+# Policy, not capability: the token count from which the training fold has been validated on the product path.  The library
+# takes towers of 512 tokens and more (hmmc_tower_fold_supported); folding those below this count would change their numerics.
+_FOLD_TRAIN_MIN_TOKENS = 2048
 
-def fold_train_enabled(tower_default, T, D, L):
-    if _FOLD_LN_TRAIN in ("0", "", "off", False) or not (_FOLD_LN_TRAIN in ("all", "1", True) or tower_default):
-        return False
-    # the shapes hmmc_tower_fwd_fused(keep_acts = 1) takes: the grouped weight-gradient launch must exist for them
-    # (the library's own switch decides - hmmc_amd/_lib.py set it from HMMC_NO_WGRAD_GROUP when it loaded the library - so that
-    # Python and the library cannot read the variable differently)
-    from ._lib import get_option
-    return (L <= 256 and D % 256 == 0 and T >= 2048 and (T + 256) * 4 * D * 2 < (1 << 31) - (1 << 24)
-            and not get_option("no_wgrad_group"))
+
+def _fold_off(switch):
+    return switch in ("0", "", "off")
+
+
+def _fold_policy(switch, tower_default):
+    """The value of one of the two switches above (read when a pass starts: bench.py and the tests assign them) -> whether a
+    tower folds.  tower_default: True for a tower that folds under the default policy (the ViT frame tower)."""
+    return not _fold_off(switch) and (switch in ("all", "1") or bool(tower_default))
 
 
 def fold_enabled(tower_default):
-    """tower_default: True for a tower that folds under the default policy (the ViT frame tower)."""
-    if _FOLD_LN in ("0", "", "off", False):
-        return False
-    if _FOLD_LN in ("all", "1", True):
-        return True
-    return bool(tower_default)
+    """Whether this tower's passes that keep no activations fold (HMMC_FOLD_LN); _tower_forward asks the library for the shape."""
+    return _fold_policy(_FOLD_LN, tower_default)
 
 
-def _tower_forward(x, params, nseq, L, heads, causal, eps, fp32, keep, lead_only=False, x_stat=None, fold=False):
-    """Run all layers through the native layer runtime (hmmc_tower_fwd).  Returns (y, acts slab or None).
-    lead_only: only token 0 of every sequence of y is defined (see include/hmmc_hip.h)."""
-    from ._lib import ERRORS, call, load, ptr, query, stream
+def fold_train_enabled(tower_default, T, D, L):
+    """Whether this tower's training pass folds at T tokens of width D in sequences of L: the switch (HMMC_FOLD_LN_TRAIN), the
+    policy's token count and the library's shape limits - hmmc_tower_fold_supported, which knows the grouped weight-gradient
+    launch the folded backward needs and the "no_wgrad_group" option (hmmc_amd/_lib.py sets it from HMMC_NO_WGRAD_GROUP)."""
+    from ._lib import query
+    return (_fold_policy(_FOLD_LN_TRAIN, tower_default) and T >= _FOLD_TRAIN_MIN_TOKENS
+            and bool(query("hmmc_tower_fold_supported", T, D, L, 1)))
+
+
+def _tower_forward(x, params, nseq, L, heads, causal, eps, fp32, keep, lead_only=False, x_stat=None, fold=False, last_exact=False):
+    """Run all layers through the native layer runtime.  Returns (y, what _tower_backward needs or None).
+    lead_only: only token 0 of every sequence of y is defined (see include/hmmc_hip.h).  fold (fp16 towers): run with ln_1 / ln_2
+    folded into the GEMMs (hmmc_tower_fwd_fused) where the library takes the shape; with keep, last_exact leaves the last layer
+    on the unfolded kernels.  x_stat: the row pairs of x for a folded pass, when its producer has them."""
+    from ._lib import call, call_status, ptr, query
     T, D = x.shape
     nl = len(params) // PER_LAYER
     slab = query("hmmc_tower_act_bytes", T, D, nseq, L, heads, int(fp32))
-    if fold and keep and not fp32:                 # folded layers keep no normalised activations: a smaller slab each
-        nfold = nl - int(fold == "last_exact")
-        acts = torch.empty(query("hmmc_tower_act_bytes_fold", T, D, nseq, L, heads) * nfold + slab * (nl - nfold), dtype=torch.uint8,
-                           device=x.device)
-    else:
-        acts = torch.empty(slab * (nl if keep else 1), dtype=torch.uint8, device=x.device)
-    if fold and not keep and not fp32 and (T + 256) * 4 * D * 2 < (1 << 31) - (1 << 24):
+    fold = bool(fold) and not fp32
+    if fold and not keep and query("hmmc_tower_fold_supported", T, D, L, 0):
+        acts = torch.empty(slab, dtype=torch.uint8, device=x.device)
         fwb = query("hmmc_tower_fold_bytes", T, D, nl, 0)
         fws = ops.workspace(fwb, x.device, "tower_fold")
         y = torch.empty_like(x)
         call("hmmc_tower_fwd_fused", ptr(x), ptr(x_stat), ptr(y), _ptr_array(params), ptr(acts), 0, nseq, L, heads, D, nl, int(causal),
              float(eps), int(lead_only), 0, ptr(fws), fwb)
         return y, None
-    if fold and keep and not fp32:
-        # training: the fold workspace (folded weights, fp32 weight-gradient sums) lives until the backward call
-        last_exact = int(fold == "last_exact")
+    if fold and keep:
+        # training: folded layers keep no normalised activations (a smaller slab each); the fold workspace (folded weights, fp32
+        # weight-gradient sums) lives until the backward call
+        nfold = nl - int(last_exact)
+        acts = torch.empty(query("hmmc_tower_act_bytes_fold", T, D, nseq, L, heads) * nfold + slab * (nl - nfold), dtype=torch.uint8,
+                           device=x.device)
         fwb = query("hmmc_tower_fold_bytes", T, D, nl, 1)
         fws = torch.empty(fwb, dtype=torch.uint8, device=x.device)
         y = torch.empty_like(x)
-        rc = getattr(load(), "hmmc_tower_fwd_fused")(ptr(x), ptr(x_stat), ptr(y), _ptr_array(params), ptr(acts), 1, nseq, L, heads, D, nl,
-                                                     int(causal), float(eps), int(lead_only), last_exact, ptr(fws), fwb, stream())
+        rc = call_status("hmmc_tower_fwd_fused", ptr(x), ptr(x_stat), ptr(y), _ptr_array(params), ptr(acts), 1, nseq, L, heads, D, nl,
+                         int(causal), float(eps), int(lead_only), int(last_exact), ptr(fws), fwb, allow="HMMC_ERR_UNSUPPORTED")
         if rc == 0:
-            return y, (acts, fws, last_exact)
-        if rc != -2:
-            raise RuntimeError(f"hmmc_tower_fwd_fused failed: {ERRORS.get(rc, rc)}")
-        # HMMC_ERR_UNSUPPORTED (nothing was launched): a shape or setting the folded training runtime does not take after all -
-        # the unfolded kernels below compute the same function
-        del fws
-        acts = torch.empty(slab * nl, dtype=torch.uint8, device=x.device)
+            return y, (acts, fws, int(last_exact))
+        # HMMC_ERR_UNSUPPORTED (nothing was launched): a shape or setting the folded training runtime does not take after all - the unfolded
+        # kernels below compute the same function
+        del acts, fws, y
+    acts = torch.empty(slab * (nl if keep else 1), dtype=torch.uint8, device=x.device)
     wsb = query("hmmc_tower_workspace_bytes", T, D, nseq, int(fp32), 0)
     ws = ops.workspace(wsb, x.device, "tower")
     y = torch.empty_like(x)
@@ -275,24 +282,29 @@ def _tower_backward(dy, x0, params, acts, nseq, L, heads, causal, fp32, lead_onl
     return dx, grads
 
 
+def _tower_args(x, params, lead_only):
+    """The checks of a CLIP tower's arguments -> (contiguous x, fp32, lead_only as the library takes it)."""
+    for prm in params:
+        if not prm.is_contiguous():
+            raise ValueError("tower parameters must be contiguous")
+    if any(prm.dtype != (x.dtype if prm.dim() == 2 else prm.dtype) for prm in params):
+        raise RuntimeError(f"expected the activations ({x.dtype}) and the tower weights to have the same dtype: after "
+                           "model.float() set text_encoder.dtype = torch.float32 as well, as with the reference")
+    fp32 = x.dtype == torch.float32
+    return x.contiguous(), fp32, bool(lead_only and not fp32)        # the class-token pruning exists for the fp16 tower only
+
+
 class ClipTransformerFn(torch.autograd.Function):
     """All layers of a CLIP tower in one autograd node and ONE native call each way (fp16 activations, fp32
     LayerNorm statistics); the per-layer activations live in a single slab laid out by the library."""
 
     @staticmethod
-    def forward(ctx, x, nseq, L, heads, causal, lead_only, fold, x_stat, *params):
+    def forward(ctx, x, nseq, L, heads, causal, lead_only, fold_train, last_exact, x_stat, *params):
         keep = any(ctx.needs_input_grad)       # no_grad passes never get here: clip_transformer() below
-        x = x.contiguous()
-        for prm in params:
-            if not prm.is_contiguous():
-                raise ValueError("tower parameters must be contiguous")
-        fp32 = x.dtype == torch.float32
-        if any(prm.dtype != (x.dtype if prm.dim() == 2 else prm.dtype) for prm in params):
-            raise RuntimeError(f"expected the activations ({x.dtype}) and the tower weights to have the same dtype: after "
-                               "model.float() set text_encoder.dtype = torch.float32 as well, as with the reference")
-        lead_only = bool(lead_only and not fp32)        # the class-token pruning exists for the fp16 tower only
-        y, acts = _tower_forward(x, params, nseq, L, heads, causal, 1e-5, fp32, keep, lead_only, fold=fold if keep else False,
-                                 x_stat=x_stat if (keep and fold) else None)
+        x, fp32, lead_only = _tower_args(x, params, lead_only)
+        fold = bool(fold_train and keep)
+        y, acts = _tower_forward(x, params, nseq, L, heads, causal, 1e-5, fp32, keep, lead_only, x_stat=x_stat if fold else None,
+                                 fold=fold, last_exact=last_exact)
         ctx.acts, ctx.x0, ctx.params = acts, (x if keep else None), params
         ctx.cfg = (nseq, L, heads, causal, lead_only, fp32)
         return y
@@ -302,38 +314,41 @@ class ClipTransformerFn(torch.autograd.Function):
         nseq, L, heads, causal, lead_only, fp32 = ctx.cfg
         dx, grads = _tower_backward(dy.contiguous(), ctx.x0, ctx.params, ctx.acts, nseq, L, heads, causal, fp32, lead_only)
         ctx.acts = ctx.x0 = None
-        return (dx, None, None, None, None, None, None, None, *grads)
+        return (dx, None, None, None, None, None, None, None, None, *grads)
 
 
-def clip_transformer(x, nseq, L, heads, causal, lead_only, *params, x_stat=None, fold=False, fold_train=False):
-    """ClipTransformerFn.apply, except that passes which record no graph (torch.no_grad(): eval, the momentum encoders of
-    modules/modeling.py:347-357) go straight to the forward-only runtime: `ctx.needs_input_grad` reports the inputs'
-    requires_grad whatever the grad mode, so until round 4 those passes kept - and wrote - every layer's activations."""
+def clip_transformer(x, nseq, L, heads, causal, lead_only, *params, x_stat=None, fold_no_acts=False, fold_train=False, last_exact=False):
+    """One run of a CLIP tower's layers; the caller (module_clip.Transformer.forward) has decided the fold: fold_no_acts for a
+    pass that keeps no activations, fold_train for a training pass, which with last_exact leaves its last layer unfolded.
+    A pass that records a graph is ClipTransformerFn.apply.  One that records none (torch.no_grad(): eval, the momentum encoders
+    of modules/modeling.py:347-357) goes straight to the forward-only runtime: inside a Function `ctx.needs_input_grad` reports
+    the inputs' requires_grad whatever the grad mode, and the pass would keep - and write - every layer's activations."""
     if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
-        return ClipTransformerFn.apply(x, nseq, L, heads, causal, lead_only, fold_train, x_stat, *params)
-    x = x.contiguous()
-    fp32 = x.dtype == torch.float32
-    if any(prm.dtype != (x.dtype if prm.dim() == 2 else prm.dtype) for prm in params):
-        raise RuntimeError(f"expected the activations ({x.dtype}) and the tower weights to have the same dtype: after "
-                           "model.float() set text_encoder.dtype = torch.float32 as well, as with the reference")
-    for prm in params:
-        if not prm.is_contiguous():
-            raise ValueError("tower parameters must be contiguous")
-    y, _ = _tower_forward(x, params, nseq, L, heads, causal, 1e-5, fp32, False, bool(lead_only and not fp32), x_stat=x_stat, fold=fold)
-    return y
+        return ClipTransformerFn.apply(x, nseq, L, heads, causal, lead_only, fold_train, last_exact, x_stat, *params)
+    x, fp32, lead_only = _tower_args(x, params, lead_only)
+    return _tower_forward(x, params, nseq, L, heads, causal, 1e-5, fp32, False, lead_only, x_stat=x_stat, fold=fold_no_acts)[0]
 
 
-# TemporalFn.forward cannot see the caller's grad mode (it is always off inside forward): temporal() sets this around apply
-_NO_GRAD_CALL = {"on": False}
+def _temporal_forward(u, heads, pos_table, params, keep):
+    """-> (video_emb, (acts, x0, x, u2, norms): what TemporalFn.backward needs)."""
+    b, F, E = u.shape
+    u2 = u.contiguous().view(b * F, E)
+    acts = x0 = None
+    if len(params) // PER_LAYER:
+        x0 = ops.add_rowbias(u2, pos_table, F)
+        x, acts = _tower_forward(x0, params, b, F, heads, False, 1e-12, True, keep)
+        out, norms = ops.temporal_pool_fwd(x, u2, b, F, E)
+    else:
+        x = u2
+        out, norms = ops.temporal_pool_fwd(x, None, b, F, E)
+    return out, (acts, x0, x, u2, norms)
 
 
 def temporal(u, heads, pos_table, *params):
-    """TemporalFn.apply; under torch.no_grad() without kept activations (see clip_transformer)."""
-    _NO_GRAD_CALL["on"] = not torch.is_grad_enabled()
-    try:
+    """TemporalFn.apply; a pass that records no graph keeps no activations (see clip_transformer)."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (u, pos_table) + params):
         return TemporalFn.apply(u, heads, pos_table, *params)
-    finally:
-        _NO_GRAD_CALL["on"] = False
+    return _temporal_forward(u, heads, pos_table, params, False)[0]
 
 
 class LnProjFn(torch.autograd.Function):
@@ -381,21 +396,10 @@ class TemporalFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, u, heads, pos_table, *params):
-        b, F, E = u.shape
-        u2 = u.contiguous().view(b * F, E)
-        nl = len(params) // PER_LAYER
-        keep = any(ctx.needs_input_grad) and not _NO_GRAD_CALL["on"]
-        acts = x0 = None
-        if nl:
-            x0 = ops.add_rowbias(u2, pos_table, F)
-            x, acts = _tower_forward(x0, params, b, F, heads, False, 1e-12, True, keep)
-            out, norms = ops.temporal_pool_fwd(x, u2, b, F, E)
-        else:
-            x = u2
-            out, norms = ops.temporal_pool_fwd(x, None, b, F, E)
+        out, (acts, x0, x, u2, norms) = _temporal_forward(u, heads, pos_table, params, any(ctx.needs_input_grad))
         ctx.acts, ctx.x0, ctx.params = acts, x0, params
         ctx.fin = (x, u2, norms, pos_table)
-        ctx.cfg = (b, F, E, heads)
+        ctx.cfg = (*u.shape, heads)
         return out
 
     @staticmethod

@@ -60,7 +60,8 @@ class Transformer(nn.Module):
         self.width, self.layers, self.heads = width, layers, heads
         self.causal = attn_mask is not None
         self.ddp_layers_per_node = 3           # world_size > 1 only: granularity of gradient hand-over to DDP
-        self.fold_ln = False                   # no-grad passes with ln_1 / ln_2 folded into the GEMMs (functional.fold_enabled)
+        self.fold_ln = False                   # this tower folds ln_1 / ln_2 into its GEMMs under the default policy ("vit") of
+                                               # functional.fold_enabled / fold_train_enabled; VisualTransformer sets it
         self.resblocks = nn.Sequential(*[ResidualAttentionBlock(width, heads, attn_mask) for _ in range(layers)])
 
     def flat_params(self):
@@ -83,16 +84,20 @@ class Transformer(nn.Module):
             from . import ops
             ops.reserve_cus_for_collectives()
         blocks = list(self.resblocks)
-        train_fold = x.dtype == torch.float16 and Fn.fold_train_enabled(self.fold_ln, x.shape[0], self.width, L)
+        # the one decision about the fold, for every run of layers below
+        fold_no_acts = Fn.fold_enabled(self.fold_ln)
+        fold_train = x.dtype == torch.float16 and Fn.fold_train_enabled(self.fold_ln, x.shape[0], self.width, L)
         for i in range(0, self.layers, per):
             params = []
             for blk in blocks[i:i + per]:
                 params += Fn.block_params(blk)
             final = i + per >= self.layers
-            # training fold: every layer but the tower's last (which, lead-only, works on 1 / L of the rows anyway)
-            ft = ("last_exact" if final else "all") if train_fold and not (final and len(params) == Fn.PER_LAYER) else False
+            # training fold: every layer but the tower's last (which, lead-only, works on 1 / L of the rows anyway), so a last
+            # run of one layer has nothing to fold
+            only_the_last_layer = final and len(params) == Fn.PER_LAYER
             x = Fn.clip_transformer(x, nseq, L, self.heads, self.causal, bool(lead_only and final), *params,
-                                    x_stat=x_stat if i == 0 else None, fold=Fn.fold_enabled(self.fold_ln), fold_train=ft)
+                                    x_stat=x_stat if i == 0 else None, fold_no_acts=fold_no_acts,
+                                    fold_train=fold_train and not only_the_last_layer, last_exact=final)
         return x
 
 

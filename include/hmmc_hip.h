@@ -465,9 +465,12 @@ int hmmc_tower_fwd(const void* x, void* y, const void* const* params, void* acts
  * the residual stream, the row statistics come out of the out_proj / c_proj epilogues.  keep_acts = 0 (eval, the momentum
  * encoders of modules/modeling.py:347-357): acts is ONE slab of hmmc_tower_act_bytes(), fold_ws hmmc_tower_fold_bytes(.., 0).
  * keep_acts = 1 (training): acts as hmmc_tower_act_bytes_fold describes, fold_ws hmmc_tower_fold_bytes(.., 1), BOTH go to hmmc_tower_bwd_fold;
- * needs D % 256 == 0, >= 2048 tokens, and last_exact when lead_only.  last_exact = 1: the LAST layer runs on the
- * unfolded kernels.  x_stat (may be NULL): the row pairs of x as hmmc_rowstat / hmmc_vit_embed_ln give them.  Returns
- * HMMC_ERR_UNSUPPORTED for operands of 2 GiB and more or shapes outside the above (use hmmc_tower_fwd). */
+ * needs last_exact when lead_only.  last_exact = 1: the LAST layer runs on the unfolded kernels.  x_stat (may be NULL): the row
+ * pairs of x as hmmc_rowstat / hmmc_vit_embed_ln give them.  Returns HMMC_ERR_UNSUPPORTED where hmmc_tower_fold_supported says 0
+ * (use hmmc_tower_fwd).
+ * hmmc_tower_fold_supported (1 / 0, reads no device state; train = keep_acts): operands below 2 GiB; train = 1 also needs
+ * L <= 256 and the grouped weight-gradient launch (D % 256 == 0, >= 512 tokens, "no_wgrad_group" off). */
+int hmmc_tower_fold_supported(long tokens, int D, int L, int train);
 size_t hmmc_tower_fold_bytes(long tokens, int D, int nlayers, int train);
 /* slab of a layer that runs folded with keep_acts = 1 (no ln_1 / ln_2 outputs are kept): acts of such a call = nfold of these
  * followed by (nlayers - nfold) slabs of hmmc_tower_act_bytes(), nfold = nlayers - (last_exact ? 1 : 0) */

@@ -429,7 +429,7 @@ def test_folded_training_tower_is_deterministic_and_chunks_agree(monkeypatch):
                 for blk in blocks[i:i + n]:
                     params += Fn.block_params(blk)
                 i += n
-                y = Fn.clip_transformer(y, nseq, L, heads, False, False, *params, fold_train="last_exact" if i == layers else "all")
+                y = Fn.clip_transformer(y, nseq, L, heads, False, False, *params, fold_train=True, last_exact=i == layers)
         (y.float() * wsel).sum().backward()
         torch.cuda.synchronize()
         return y.detach().clone(), x.grad.clone(), [q.grad.clone() for blk in tw.resblocks for q in Fn.block_params(blk)]

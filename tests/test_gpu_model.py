@@ -255,6 +255,21 @@ def test_temporal_fn_vs_oracle():
         close(P[k].grad, sdo[k].grad, 2e-5, 2e-3, k)
 
 
+def test_temporal_without_a_transformer_takes_an_input_that_records_no_graph():
+    """use_temp = False: module_cross.py calls Fn.temporal(frame_output, 0, None).  With the grad mode on and a frame_output
+    that does not require grad (a frozen frame tower) the pass records no graph and computes what the recording one does."""
+    u = synth.normal("temporal.nograph.u", (5, 4, 512)).to(DEV)
+    assert torch.is_grad_enabled()
+    out = Fn.temporal(u, 0, None)
+    assert not out.requires_grad
+    ug = u.clone().requires_grad_()
+    rec = Fn.temporal(ug, 0, None)
+    assert rec.requires_grad and torch.equal(out, rec.detach())
+    with torch.no_grad():
+        assert torch.equal(out, Fn.temporal(ug, 0, None))
+    close(out, (u / u.norm(dim=-1, keepdim=True)).mean(1).cpu(), 2e-5, 1e-4, "video_emb")   # the bound test_temporal_fn_vs_oracle holds this output to
+
+
 # ----------------------------------------------------------------------------- full model
 
 def build(dims, use_temp=True, **tc):

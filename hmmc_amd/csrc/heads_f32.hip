@@ -5,6 +5,7 @@
 //   * eval-time top-k-frames mean                        (main_task_retrieval.py:332-336)
 //   * temporal pooling  mean_f( (h+u)/||h+u|| )          (modules/module_cross.py:207-212)
 //   * the temporal transformer's F x F fp32 attention    (modules/module_cross.py:127-131)
+//   * the MLM pass's BERT masking of the token ids      (modules/modeling.py:181-205)
 // The similarity logits themselves come from hmmc_gemm_f32 as ONE [B, B*(1+F)] matrix
 // S_all = 100 * Qn [Vn ; Un]^T: column c < B is video c, column B + b*F + f is frame f of video b,
 // so the reference's F+1 separate matmuls and 2(F+1) log-softmax passes become one GEMM and three
@@ -227,6 +228,24 @@ __global__ __launch_bounds__(256) void add_rowbias_kernel(const float* __restric
     f4 a = *reinterpret_cast<const f4*>(x + r * D + c);
     f4 t = *reinterpret_cast<const f4*>(table + (long)(r % period) * D + c);
     *reinterpret_cast<f4*>(out + r * D + c) = a + t;
+  }
+}
+
+// ---------------------------------------------------------------- MLM masking (modules/modeling.py:181-205), per element
+// m = masked && id != pad && id != cls; label = m ? id : -100; id' = m && replaced ? mask_id : (m && randsel ? word : id).
+// The draws are bytes (torch.bool); ids_out may be ids itself (each element is read before it is written, by the same lane).
+__global__ __launch_bounds__(256) void mlm_mask_kernel(const long* ids, const unsigned char* __restrict__ masked,
+                                                       const unsigned char* __restrict__ replaced,
+                                                       const unsigned char* __restrict__ randsel, const long* __restrict__ words,
+                                                       long pad_id, long cls_id, long mask_id, long* ids_out, long* labels_out,
+                                                       long n) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const long id = ids[i];
+    const bool m = masked[i] != 0 && id != pad_id && id != cls_id;
+    const bool rep = m && replaced[i] != 0;
+    const bool rnd = m && !rep && randsel[i] != 0;
+    ids_out[i] = rep ? mask_id : (rnd ? words[i] : id);
+    if (labels_out) labels_out[i] = m ? id : -100;
   }
 }
 
@@ -558,5 +577,14 @@ extern "C" int hmmc_temporal_attention_bwd(const float* qkv, const float* probs,
   }
   size_t lds = (size_t)(4 * F * 65 + 2 * F * F) * sizeof(float);
   hmmc_launch_lds<tattn_bwd_kernel>(HMMC_LDS_MOST, dim3(b * H), dim3(64), lds, stream, qkv, probs, dout, dqkv, F, H);
+  return hmmc_launch_status();
+}
+
+extern "C" int hmmc_mlm_mask(const long* ids, const unsigned char* masked, const unsigned char* replaced,
+                             const unsigned char* randsel, const long* words, long pad_id, long cls_id, long mask_id,
+                             long* ids_out, long* labels_out, long n, hipStream_t stream) {
+  if (!ids || !masked || !replaced || !randsel || !words || !ids_out || n <= 0) return HMMC_ERR_ARG;
+  hipLaunchKernelGGL(mlm_mask_kernel, dim3(nblk(n)), dim3(256), 0, stream, ids, masked, replaced, randsel, words, pad_id, cls_id,
+                     mask_id, ids_out, labels_out, n);
   return hmmc_launch_status();
 }

@@ -776,3 +776,67 @@ def bert_text(ids, mask, cfg, want, pool_w, pool_b, proj_w, proj_b, *params):
     """BertFn.apply; a pass that records no graph (torch.no_grad(): eval) keeps no activations."""
     keep = torch.is_grad_enabled() and any(p.requires_grad for p in (pool_w, pool_b, proj_w, proj_b) + params)
     return BertFn.apply(ids, mask, cfg, want, keep, pool_w, pool_b, proj_w, proj_b, *params)
+
+
+class BertManyFn(torch.autograd.Function):
+    """Several text inputs through ONE pass of the Chinese tower (TextEncoder.encode_many): ids / mask [R, L] hold the
+    inputs' rows one after the other, padded to the longest; segs = ((row0, b, want), ...).  want = "feat": pooler + text_proj
+    on the segment's class rows, addressed in place -> [b, E]; "hidden": text_proj of ALL L positions of the segment's rows
+    -> [b, L, E] (the caller slices a shorter input's positions off outside this node, so the padded ones get exact zeros on
+    the way back).  The backward assembles one dy and runs one hmmc_bert_bwd: one gradient per parameter."""
+
+    @staticmethod
+    def forward(ctx, ids, mask, cfg, segs, keep, pool_w, pool_b, proj_w, proj_b, *params):
+        for prm in (pool_w, pool_b, proj_w, proj_b) + params:
+            if prm.dtype != torch.float32 or not prm.is_cuda or not prm.is_contiguous():
+                raise TypeError("the Chinese text encoder runs in fp32 on contiguous CUDA parameters")
+        R, L = ids.shape
+        y, acts = _bert_tower_forward(ids, mask, params, cfg, keep)
+        outs, pooled = [], []
+        for row0, b, want in segs:
+            rows = y[row0 * L:(row0 + b) * L]
+            if want == "feat":
+                pooled.append(ops.bert_pooler_fwd(rows, pool_w, pool_b, b, L))
+                outs.append(ops.linear_f32(pooled[-1], proj_w, bias=proj_b))
+            else:
+                pooled.append(None)
+                outs.append(ops.linear_f32(rows, proj_w, bias=proj_b).view(b, L, -1))
+        if keep:
+            ctx.save_for_backward(ids, mask, y, pool_w, proj_w, *[t for t in pooled if t is not None])
+            ctx.acts, ctx.params, ctx.cfg, ctx.segs = acts, params, cfg, segs
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *douts):
+        ids, mask, y, pool_w, proj_w, *kept = ctx.saved_tensors
+        R, L = ids.shape
+        D = y.shape[1]
+        dy = torch.zeros_like(y)                           # the pooler backward writes class rows only
+        acc = {}
+
+        def add(name, g):
+            acc[name] = g if name not in acc else acc[name].add_(g)
+
+        for (row0, b, want), dout in zip(ctx.segs, douts):
+            d = dout.contiguous().view(-1, dout.shape[-1])
+            rows, drows = y[row0 * L:(row0 + b) * L], dy[row0 * L:(row0 + b) * L]
+            add("proj_b", ops.colsum(d))
+            if want == "feat":
+                pooled = kept.pop(0)
+                add("proj_w", ops.wgrad_f32(d, pooled))
+                dpool_w, dpool_b = ops.bert_pooler_bwd(ops.dgrad_f32(d, proj_w), pooled, rows, pool_w, b, L, drows)
+                add("pool_w", dpool_w)
+                add("pool_b", dpool_b)
+            else:
+                add("proj_w", ops.wgrad_f32(d, rows))
+                E = d.shape[1]
+                ops.gemm_f32(d, proj_w, b * L, D, E, (E, 1), (D, 1), out=drows)          # d @ proj_w into the segment's rows
+        grads = _bert_tower_backward(dy, ids, mask, ctx.params, ctx.acts, ctx.cfg)
+        ctx.acts = None
+        return (None, None, None, None, None, acc.get("pool_w"), acc.get("pool_b"), acc["proj_w"], acc["proj_b"], *grads)
+
+
+def bert_text_many(ids, mask, cfg, segs, pool_w, pool_b, proj_w, proj_b, *params):
+    """BertManyFn.apply; a pass that records no graph (the momentum encoder) keeps no activations."""
+    keep = torch.is_grad_enabled() and any(p.requires_grad for p in (pool_w, pool_b, proj_w, proj_b) + params)
+    return BertManyFn.apply(ids, mask, cfg, tuple(segs), keep, pool_w, pool_b, proj_w, proj_b, *params)

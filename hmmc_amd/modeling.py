@@ -15,7 +15,7 @@ from torch import nn
 from . import functional as Fn
 from . import ops
 from .module_clip import dims_from_state_dict
-from .module_cross import BertLMPredictionHead, CrossConfig, TextEncoder, VisualEncoder
+from .module_cross import BertLMPredictionHead, CrossConfig, TextEncoder, VisualEncoder, bert_tokenizer_constants
 from .until_module import CrossEn, PreTrainedModel
 
 logger = logging.getLogger(__name__)
@@ -122,10 +122,6 @@ class BirdPreTrainedModel(CLIP4ClipPreTrainedModel):
 
     def __init__(self, cross_config, task_config):
         super(BirdPreTrainedModel, self).__init__(cross_config)
-        if getattr(task_config, "language", "english") == "chinese":
-            raise NotImplementedError("pre-training with language = \"chinese\" is not implemented: the MLM head needs the "
-                                      "BertTokenizer vocabulary (size, [MASK] / [PAD] / [CLS] ids) and TextEncoder.encode_many "
-                                      "needs attention masks; fine-tuning and eval (BirdModel) support the Chinese encoder")
         self.task_config = task_config
         self.rank = task_config.local_rank
         self.mlm_probability = cross_config.mlm_probability
@@ -136,8 +132,14 @@ class BirdPreTrainedModel(CLIP4ClipPreTrainedModel):
         self.contrast_temperature = task_config.contrast_temperature
         self.contrast_num_negative = task_config.contrast_num_negative
         E = cross_config.temporal_hidden_size
+        if getattr(task_config, "language", "english") == "chinese":
+            # the reference's BertTokenizer.from_pretrained(pretrained_text) (modules/modeling.py:104-120): ids and size per instance
+            tok = bert_tokenizer_constants(getattr(task_config, "pretrained_text", None))
+            self.PAD_ID, self.CLS_ID, self.MASK_ID, self.VOCAB = tok["pad_id"], tok["cls_id"], tok["mask_id"], tok["vocab_size"]
         self.text_encoder = TextEncoder(self.task_config, cross_config)
         self.text_encoder_k = TextEncoder(self.task_config, cross_config)
+        if self.text_encoder.language == "chinese":
+            self.text_encoder.pad_id = self.text_encoder_k.pad_id = self.PAD_ID      # encode_many pads with the tokenizer's [PAD]
         self.t_projector = MLP(num_layers=cross_config.proj_num_layers)
         self.t_projector_k = MLP(num_layers=cross_config.proj_num_layers)
         self.cls = BertLMPredictionHead(E, self.VOCAB, "gelu")
@@ -161,7 +163,8 @@ class BirdPreTrainedModel(CLIP4ClipPreTrainedModel):
         self.register_load_state_dict_post_hook(lambda module, incompatible_keys: setattr(module, "_queue_ptr_host", None))
         self.loss_fct = CrossEn()
         self._ema_table = None
-        self._mlm_draws = None          # tests inject the reference's recorded random draws here
+        self._mlm_draws = None          # tests inject the reference's recorded random draws here: four tensors, or a list of
+        self._mlm_draw_calls = 0        # such sets taken in turn by the mask() calls
 
     # ---- momentum encoders
     @torch.no_grad()
@@ -241,10 +244,17 @@ class BirdPreTrainedModel(CLIP4ClipPreTrainedModel):
         return t2f + f2t
 
     def mask(self, input_ids, vocab_size, device, targets=None, masked_indices=None, probability_matrix=None):
-        """BERT masking with the reference's quirks (modules/modeling.py:181-205): never masks EOT (its "pad") or SOT;
-        80% [MASK]=49394, 10% random id; the random draws are made on the CPU like the reference's."""
+        """BERT masking with the reference's quirks (modules/modeling.py:181-205): never masks the tokenizer's pad (EOT for
+        CLIP's) or [CLS] / SOT; 80% [MASK], 10% random id; the random draws are made on the CPU like the reference's.  In place
+        on input_ids and targets.  On the GPU the draws are applied by one launch (hmmc_mlm_mask; targets, a copy of the ids in
+        every caller, receive the id at the masked positions and -100 elsewhere): indexing with a boolean tensor, as the
+        reference does, reads a count on the host and stalls the launch stream every step."""
         if self._mlm_draws is not None:
-            masked, replaced, randsel, words = [t.to(input_ids.device) for t in self._mlm_draws]
+            draws = self._mlm_draws
+            if not torch.is_tensor(draws[0]):           # one set of four per call of a step (the `bird` branch makes two)
+                draws = draws[self._mlm_draw_calls % len(draws)]
+                self._mlm_draw_calls += 1
+            masked, replaced, randsel, words = [t.to(input_ids.device) for t in draws]
             masked, replaced, randsel = masked.bool(), replaced.bool(), randsel.bool()
         else:
             shape = input_ids.shape
@@ -252,6 +262,16 @@ class BirdPreTrainedModel(CLIP4ClipPreTrainedModel):
             replaced = torch.bernoulli(torch.full(shape, 0.8)).bool().to(input_ids.device)
             randsel = torch.bernoulli(torch.full(shape, 0.5)).bool().to(input_ids.device)
             words = torch.randint(vocab_size, shape, dtype=torch.long).to(input_ids.device)
+        if input_ids.is_cuda:
+            ids = input_ids if input_ids.is_contiguous() else input_ids.contiguous()
+            lab = targets if targets is None or targets.is_contiguous() else targets.contiguous()
+            ops.mlm_mask_(ids, masked.contiguous(), replaced.contiguous(), randsel.contiguous(), words.contiguous(),
+                          self.PAD_ID, self.CLS_ID, self.MASK_ID, labels=lab)
+            if ids is not input_ids:
+                input_ids.copy_(ids)
+            if lab is not targets:
+                targets.copy_(lab)
+            return (input_ids, targets) if targets is not None else input_ids
         masked = masked.clone()
         masked[input_ids == self.PAD_ID] = False
         masked[input_ids == self.CLS_ID] = False
@@ -268,8 +288,13 @@ class BirdPreTrainedModel(CLIP4ClipPreTrainedModel):
         ids = input_ids.clone()
         labels = ids.clone()
         prob = torch.full(labels.shape, self.mlm_probability)
-        # random replacement ids are drawn from the rows the embedding table really has (VOCAB for CLIP's tokenizer)
-        vocab = self.text_encoder.token_embedding.weight.shape[0]
+        if self.text_encoder.language == "chinese":
+            vocab = self.VOCAB                  # the tokenizer's vocab_size, as the reference (modules/modeling.py:164)
+        else:
+            # random replacement ids are drawn from the rows the embedding table really has (VOCAB for CLIP's tokenizer)
+            vocab = self.text_encoder.token_embedding.weight.shape[0]
+        # `labels` IS a copy of the ids: on the GPU mask() writes label = id at the masked positions (hmmc_mlm_mask), which equals
+        # the reference's "leave targets as they are there" only for such targets
         return self.mask(ids, vocab, input_ids.device, targets=labels, probability_matrix=prob)
 
     def get_mlm_loss(self, input_ids, input_mask):
@@ -304,16 +329,20 @@ class BirdPreTrainedModel(CLIP4ClipPreTrainedModel):
         if not bird:
             mlm_ids, mlm_labels = self._mlm_inputs(title_ids)
 
+        def masks_of(*masks):
+            # the only language branch of the step: the BERT tower needs the attention masks, the causal CLIP tower none
+            return ([*masks],) if self.text_encoder.language == "chinese" else ()
+
         def online_text():
             if bird:
                 return self.text_encoder(tag_ids, tag_mask), self.text_encoder(title_ids, title_mask), None
-            title, hidden = self.text_encoder.encode_many([title_ids, mlm_ids], ["feat", "hidden"])
+            title, hidden = self.text_encoder.encode_many([title_ids, mlm_ids], ["feat", "hidden"], *masks_of(title_mask, title_mask))
             return None, title, hidden
 
         def key_text():
             if bird:
                 return self.text_encoder_k(tag_ids, tag_mask), self.text_encoder_k(title_ids, title_mask)
-            return self.text_encoder_k.encode_many([tag_ids, title_ids], ["feat", "feat"])
+            return self.text_encoder_k.encode_many([tag_ids, title_ids], ["feat", "feat"], *masks_of(tag_mask, title_mask))
         if overlap:
             # The text towers (online title / tag features, momentum text encoder) run on a side stream beside the two frame
             # towers; the momentum pass waits for the EMA update, which stays on the main stream.  Autograd replays each

@@ -229,6 +229,29 @@ def _bert_config(path):
     return cfg
 
 
+def bert_tokenizer_constants(path):
+    """<pretrained_text>/vocab.txt as BertTokenizer indexes it (one token per line, id = line number, the trailing newline
+    stripped) -> {"vocab_size", "pad_id", "cls_id", "mask_id"}: what the pre-training model takes from its tokenizer
+    (reference modules/modeling.py:104-120,164,185-194).  The size is checked against the word-embedding table of config.json."""
+    vocab_file = os.path.join(path, "vocab.txt") if path and os.path.isdir(path) else None
+    if not vocab_file or not os.path.exists(vocab_file):
+        raise NotImplementedError("pre-training with language = \"chinese\" takes the BertTokenizer vocabulary (its size and the "
+                                  f"[MASK] / [PAD] / [CLS] ids) from <pretrained_text>/vocab.txt: no such file at {path!r}")
+    with open(vocab_file, "r", encoding="utf-8") as fh:
+        tokens = [line.rstrip("\n") for line in fh.readlines()]
+    index = {tok: i for i, tok in enumerate(tokens)}
+    out = {"vocab_size": len(tokens)}
+    for key, tok in (("pad_id", "[PAD]"), ("cls_id", "[CLS]"), ("mask_id", "[MASK]")):
+        if tok not in index:
+            raise ValueError(f"{vocab_file}: the special token {tok} is missing")
+        out[key] = index[tok]
+    embedding_rows = _bert_config(path)["vocab_size"]
+    if out["vocab_size"] > embedding_rows:
+        raise ValueError(f"{vocab_file}: vocab_size {out['vocab_size']} is larger than the encoder's word-embedding table "
+                         f"({embedding_rows} rows)")
+    return out
+
+
 class TextEncoder(nn.Module):
     """CLIP text transformer (english) or a BERT encoder + text_proj (chinese); reference modules/module_cross.py:240-305."""
 
@@ -248,6 +271,9 @@ class TextEncoder(nn.Module):
                 raise ValueError(f"cross_config.chinese_hidden_size ({cross_config.chinese_hidden_size}) is not the encoder's "
                                  f"hidden_size ({self.bert_config['hidden_size']})")
             self.dtype = torch.float32
+            # the id encode_many pads shorter inputs with (those positions carry mask 0 and are never read): config.json's
+            # pad_token_id here; a model that owns the tokenizer's constants (BirdPreTrainedModel) assigns its [PAD] id
+            self.pad_id = int(self.bert_config.get("pad_token_id", 0) or 0)
             return
         if self.language != "english":
             raise NotImplementedError(f"language {self.language!r}: the text encoder is the CLIP transformer (\"english\") or a "
@@ -315,13 +341,17 @@ class TextEncoder(nn.Module):
         return feat
 
 
-def _encode_many(self, texts, wants):
+def _encode_many(self, texts, wants, masks=None):
     """Several id tensors [b_i, L_i] through ONE pass of the text tower (padded with id 0 to the longest; the tower is
     causal and its rows independent, so every sequence's feature / hidden states are those of its own pass): one set of
     ~600 small launches instead of one per input, and ONE gradient per parameter where separate passes make autograd
     add two (the pre-training step runs the online title pass and the MLM pass of the masked titles on the same
     weights, modules/modeling.py:347-352,160-169, and two momentum passes, :369-373).
-    wants[i]: "feat" -> [b_i, 512] (EOT row), "hidden" -> [b_i, L_i, 512]."""
+    wants[i]: "feat" -> [b_i, 512] (EOT row), "hidden" -> [b_i, L_i, 512].
+    masks[i]: the attention mask of texts[i] (None: every token is real).  The Chinese tower needs them (shorter inputs are
+    padded with [PAD] and mask 0); the CLIP tower is causal and reads its EOT row, so it ignores them."""
+    if self.language == "chinese":
+        return _encode_many_chinese(self, texts, wants, masks)
     Lmax = max(t.shape[1] for t in texts)
     if Lmax > self.positional_embedding.shape[0]:
         raise ValueError("sequence longer than the positional embedding table")
@@ -343,6 +373,47 @@ def _encode_many(self, texts, wants):
             outs.append(Fn.LnProjFn.apply(x, idx, self.ln_final.weight, self.ln_final.bias, self.text_projection).view(b, L, -1))
         row0 += b
     return outs
+
+
+def _encode_many_chinese(self, texts, wants, masks):
+    """ONE hmmc_bert_fwd over all rows (and one hmmc_bert_bwd: one gradient per parameter); a "feat" segment's pooler reads
+    its class rows in place, a "hidden" segment's text_proj runs over its rows (functional.BertManyFn).  One dropout seed per
+    call, as for every tower call."""
+    cfg = self.bert_config
+    if masks is None:
+        masks = [None] * len(texts)
+    Lmax = max(t.shape[1] for t in texts)
+    if Lmax > cfg["max_position_embeddings"]:
+        raise ValueError("sequence longer than the position embedding table")
+    if Lmax > 256:
+        raise ValueError("the masked attention kernels take at most 256 tokens")
+    pad = int(self.pad_id)
+    ids, ms, segs, row0 = [], [], [], 0
+    for t, m, want in zip(texts, masks, wants):
+        if not t.is_cuda:
+            raise TypeError(f"input_ids: expected a cuda tensor, got {t.device}")
+        b, L = t.shape
+        m = torch.ones_like(t) if m is None else m.reshape(b, L)
+        if not m.is_cuda:
+            raise TypeError(f"attention_mask: expected a cuda tensor, got {m.device}")
+        t, m = t.to(torch.int64), m.to(torch.int64)
+        if L < Lmax:
+            t = torch.nn.functional.pad(t, (0, Lmax - L), value=pad)
+            m = torch.nn.functional.pad(m, (0, Lmax - L), value=0)
+        ids.append(t)
+        ms.append(m)
+        segs.append((row0, b, want))
+        row0 += b
+    ph = float(cfg.get("hidden_dropout_prob", 0.0)) if self.training else 0.0
+    pa = float(cfg.get("attention_probs_dropout_prob", 0.0)) if self.training else 0.0
+    seed = Fn.bert_seed() if (ph > 0 or pa > 0) else 0
+    enc = self.chinese_encoder
+    call_cfg = (cfg["num_attention_heads"], cfg["intermediate_size"], float(cfg.get("layer_norm_eps", 1e-12)), ph, pa, seed)
+    outs = Fn.bert_text_many(torch.cat(ids, dim=0).contiguous(), torch.cat(ms, dim=0).contiguous(), call_cfg, segs,
+                             enc.pooler.dense.weight, enc.pooler.dense.bias, self.text_proj.weight, self.text_proj.bias,
+                             *enc.flat_params())
+    # a shorter input's padded positions are sliced off OUTSIDE the node: their gradient is exactly zero
+    return [o if want == "feat" or t.shape[1] == Lmax else o[:, :t.shape[1]] for o, t, want in zip(outs, texts, wants)]
 
 
 TextEncoder.encode_many = _encode_many

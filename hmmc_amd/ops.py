@@ -788,6 +788,24 @@ def ce_bwd_(logits, labels, lse, gout, count):
     return logits
 
 
+def mlm_mask_(ids, masked, replaced, randsel, words, pad_id, cls_id, mask_id, labels=None):
+    """BERT masking applied in place to ids (and labels, when given): one launch, no host read (hmmc_mlm_mask).  masked /
+    replaced / randsel: torch.bool draws of ids' shape; words: int64 replacement ids."""
+    _chk(ids, torch.int64, "ids")
+    _chk(words, torch.int64, "words")
+    for t, n in ((masked, "masked"), (replaced, "replaced"), (randsel, "randsel")):
+        _chk(t, torch.bool, n)
+    for t in (masked, replaced, randsel, words) + (() if labels is None else (labels,)):
+        if t.numel() != ids.numel():
+            raise ValueError("mlm_mask_: the draws and the labels must have the ids' shape")
+    if labels is not None:
+        _chk(labels, torch.int64, "labels")
+    if ids.numel():
+        call("hmmc_mlm_mask", ptr(ids), ptr(masked), ptr(replaced), ptr(randsel), ptr(words), int(pad_id), int(cls_id), int(mask_id),
+             ptr(ids), ptr(labels), ids.numel())
+    return ids, labels
+
+
 # ---------------------------------------------------------------------------- the Chinese text branch (csrc/bert_f32.hip)
 
 BERT_EMB_PARAMS, BERT_LAYER_PARAMS = 5, 16          # pointer order: include/hmmc_hip.h, hmmc_bert_fwd

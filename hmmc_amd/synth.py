@@ -157,9 +157,13 @@ def finetune_state(dims: Dims, seed=42, use_temp=True):
 def pretrain_state(dims: Dims, K: int, max_frames: int, seed=42):
     """BirdPreTrainedModel state_dict; the *_k copies equal the online weights
     (copy_params, modules/modeling.py:231-236)."""
+    return _pretrain_state(text_encoder_state(dims, seed=seed), dims.vocab, dims, K, max_frames, seed)
+
+
+def _pretrain_state(t, vocab, dims, K, max_frames, seed):
+    """t: the text encoder's tensors under "text_encoder."; vocab: the tokenizer's size (rows of the MLM decoder)."""
     sd = {}
     e = dims.embed_dim
-    t = text_encoder_state(dims, seed=seed)
     v = visual_encoder_state(dims, seed=seed)
     sd.update(t)
     sd.update({k.replace("text_encoder.", "text_encoder_k.", 1): x.clone() for k, x in t.items()})
@@ -169,12 +173,12 @@ def pretrain_state(dims: Dims, K: int, max_frames: int, seed=42):
         if name != "v_predictor":
             sd.update({k.replace(name + ".", name + "_k.", 1): x.clone() for k, x in m.items()})
     # MLM head (modules/module_cross.py:308-357)
-    sd["cls.bias"] = normal("cls.bias", (dims.vocab,), 0.02, seed=seed)
+    sd["cls.bias"] = normal("cls.bias", (vocab,), 0.02, seed=seed)
     sd["cls.transform.dense.weight"] = normal("cls.transform.dense.weight", (e, e), e ** -0.5, seed=seed)
     sd["cls.transform.dense.bias"] = normal("cls.transform.dense.bias", (e,), 0.02, seed=seed)
     sd["cls.transform.LayerNorm.weight"] = normal("cls.transform.LayerNorm.weight", (e,), 0.1, 1.0, seed=seed)
     sd["cls.transform.LayerNorm.bias"] = normal("cls.transform.LayerNorm.bias", (e,), 0.05, seed=seed)
-    sd["cls.decoder.weight"] = normal("cls.decoder.weight", (dims.vocab, e), 0.02, seed=seed)
+    sd["cls.decoder.weight"] = normal("cls.decoder.weight", (vocab, e), 0.02, seed=seed)
     sd["cls.decoder.bias"] = sd["cls.bias"]
     sd.update(v)
     sd.update({k.replace("visual_encoder.", "visual_encoder_k.", 1): x.clone() for k, x in v.items()})
@@ -328,3 +332,34 @@ def finetune_batch_zh(b, f, length, vocab, res=224, seed=42, tag="zh", lens=None
     ids, mask = zh_token_ids(f"{tag}.query_ids", b, length, vocab, seed=seed, lens=lens)
     vid = video(f"{tag}.video", b, f, res, seed=seed)
     return ids, mask, vid, torch.full((b,), f, dtype=torch.long), torch.arange(b)
+
+
+ZH_UNK, ZH_MASK = 100, 103                                                  # BertTokenizer ids of [UNK] / [MASK]
+
+
+def bert_vocab_lines(dims: BertDims):
+    """The lines of a synthetic <pretrained_text>/vocab.txt: exactly dims.vocab_size tokens, the specials at BertTokenizer's
+    ids ([PAD] 0, [UNK] 100, [CLS] 101, [SEP] 102, [MASK] 103), [unusedN] below them as in the published vocabularies."""
+    special = {ZH_PAD: "[PAD]", ZH_UNK: "[UNK]", ZH_CLS: "[CLS]", ZH_SEP: "[SEP]", ZH_MASK: "[MASK]"}
+    return [special.get(i, f"[unused{i}]" if i < ZH_UNK else f"tok{i}") for i in range(dims.vocab_size)]
+
+
+def write_bert_vocab(directory, dims: BertDims, lines=None):
+    """Write vocab.txt into a <pretrained_text> directory, one token per line."""
+    import os
+    with open(os.path.join(directory, "vocab.txt"), "w", encoding="utf-8") as fh:
+        fh.write("".join(tok + "\n" for tok in (bert_vocab_lines(dims) if lines is None else lines)))
+
+
+def pretrain_state_zh(dims: Dims, bdims: BertDims, K: int, max_frames: int, seed=42):
+    """BirdPreTrainedModel(language = "chinese") state_dict: the BERT encoder (and its momentum copy) in place of the CLIP text
+    tower, the MLM decoder at the BertTokenizer's vocabulary size."""
+    return _pretrain_state(bert_state(bdims, seed=seed, embed_dim=dims.embed_dim), bdims.vocab_size, dims, K, max_frames, seed)
+
+
+def pretrain_batch_zh(b, f, vocab, title_len=45, tag_len=25, res=224, seed=42, tag="ptzh", title_lens=None, tag_lens=None):
+    """(video, video_frame, tag_ids, tag_mask, title_ids, title_mask) with BertTokenizer-style ids and masks."""
+    title, tmask = zh_token_ids(f"{tag}.title_ids", b, title_len, vocab, seed=seed, lens=title_lens)
+    tg, gmask = zh_token_ids(f"{tag}.tag_ids", b, tag_len, vocab, seed=seed, lens=tag_lens)
+    vid = video(f"{tag}.video", b, f, res, seed=seed)
+    return vid, torch.full((b,), f, dtype=torch.long), tg, gmask, title, tmask

@@ -375,6 +375,14 @@ int hmmc_ce_fwd(const float* logits, const long* labels, float* lse, float* rowl
                 hmmc_stream_t stream);
 int hmmc_ce_bwd(float* logits, const long* labels, const float* lse, const float* grad_out, const float* count, int R, long V,
                 hmmc_stream_t stream);
+/* BERT masking of the MLM pass applied to n token ids (modules/modeling.py:181-205), per element and in integers:
+ *   m = masked && id != pad_id && id != cls_id;  labels_out = m ? id : -100 (labels_out may be NULL);
+ *   ids_out = m && replaced ? mask_id : (m && !replaced && randsel ? words : id).
+ * masked / replaced / randsel: the three Bernoulli draws as bytes (0 = false), words: the random replacement ids; all four are
+ * drawn by the caller.  ids_out may be ids (in place).  One launch, nothing is read on the host. */
+int hmmc_mlm_mask(const long* ids, const unsigned char* masked, const unsigned char* replaced, const unsigned char* randsel,
+                  const long* words, long pad_id, long cls_id, long mask_id, long* ids_out, long* labels_out, long n,
+                  hmmc_stream_t stream);
 
 /* ---- The Chinese text branch (language = "chinese", modules/module_cross.py:257-265,273-277): a HuggingFace BertModel, post-LN,
  * erf-GELU, LayerNorm eps 1e-12, all fp32 (hmmc_gemm_f32 for every GEMM, nothing rounded to fp16).

@@ -19,44 +19,6 @@ namespace {
 
 constexpr float LOG2E = 1.4426950408889634f;
 
-
-// Global -> registers in LANE ORDER: lane l takes row (l >> 3) + 8 i, bytes 16 (l & 7) .. +15 of the [L][64] operand, so
-// every wave-instruction reads 8 full 128-byte rows with consecutive lanes on consecutive bytes.  (Loading the MFMA
-// fragments directly - lane (c, g) on row c, 16 bytes at 64 ks + 16 g - puts 16 consecutive lanes on 16 different rows:
-// the memory pipeline then handles 64 separate 16-byte pieces per instruction; scratch/ubench/burst_store.hip measures
-// 3.4x between the two orders.)  Rows past L are clamped, never masked.
-template <int KT>
-__device__ __forceinline__ void load_rows(const half_t* src, long ld, int L, u4v (&raw)[2 * KT], int lane) {
-#pragma unroll
-  for (int i = 0; i < 2 * KT; ++i) {
-    const int row = min((lane >> 3) + 8 * i, L - 1);
-    raw[i] = *reinterpret_cast<const u4v*>(src + (long)row * ld + 8 * (lane & 7));
-  }
-}
-// ... -> the wave's LDS tile (row-major, LDS_STRIDE) -> MFMA row fragments f[t][ks] = rows 16 t + (lane & 15), halves
-// 32 ks + 8 (lane >> 4) .. +7.  The tile keeps the operand afterwards (the transposed reads use it).
-template <int KT>
-__device__ __forceinline__ void rows_to_frags(half_t* tile, const u4v (&raw)[2 * KT], h8 (&f)[KT][2], int lane) {
-#pragma unroll
-  for (int i = 0; i < 2 * KT; ++i)
-    *reinterpret_cast<u4v*>(tile + ((lane >> 3) + 8 * i) * LDS_STRIDE + 8 * (lane & 7)) = raw[i];
-#pragma unroll
-  for (int t = 0; t < KT; ++t)
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-      f[t][ks] = *reinterpret_cast<const h8*>(tile + (t * 16 + (lane & 15)) * LDS_STRIDE + ks * 32 + 8 * (lane >> 4));
-}
-
-// store the wave's [LP][64] operand (row fragments in registers) into its LDS tile, row-major
-template <int KT>
-__device__ __forceinline__ void frags_to_tile(half_t* tile, const h8 (&f)[KT][2], int lane) {
-#pragma unroll
-  for (int t = 0; t < KT; ++t)
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-      *reinterpret_cast<h8*>(tile + (t * 16 + (lane & 15)) * LDS_STRIDE + ks * 32 + 8 * (lane >> 4)) = f[t][ks];
-}
-
 // Row 0 of a [L][64] operand in the lane order of load_rows (lanes 0-7: its 128 bytes), every other row of the first 16 as zeros.
 __device__ __forceinline__ void load_lead_row(const half_t* src, u4v (&raw)[2], int lane) {
   const u4v v = *reinterpret_cast<const u4v*>(src + 8 * (lane & 7));

@@ -699,74 +699,136 @@ def bert_seed():
     return int(torch.randint(0, 1 << 62, (1,), dtype=torch.int64).item())
 
 
-def _bert_tower_forward(ids, mask, params, cfg, keep):
-    """hmmc_bert_fwd: -> (last_hidden_state [b*L, D], acts or None)."""
+_BERT_LN_SLOTS = (8, 9, 14, 15)                      # the LayerNorm weight / bias of a layer's 16 entries (hmmc_bert_fwd's order)
+
+
+def bert_layout_regime(pool_w, pool_b, proj_w, proj_b, params):
+    """The regime a dtype layout selects (dtypes only; module_cross.bert_regime is this function on a TextEncoder's tensors):
+    torch.float32 when every parameter is fp32; torch.float16 for exactly module_cross.convert_bert_weights' layout (every
+    dense weight and bias fp16; the embedding tables and every LayerNorm parameter fp32).  Anything else raises."""
+    fixed = list(params[:ops.BERT_EMB_PARAMS])
+    dense = [pool_w, pool_b, proj_w, proj_b]
+    for i, prm in enumerate(params[ops.BERT_EMB_PARAMS:]):
+        (fixed if i % ops.BERT_LAYER_PARAMS in _BERT_LN_SLOTS else dense).append(prm)
+    if all(t.dtype == torch.float32 for t in fixed):
+        for dt in (torch.float32, torch.float16):
+            if all(t.dtype == dt for t in dense):
+                return dt
+    mixed = sorted({str(t.dtype) for t in fixed + dense})
+    raise TypeError(f"the Chinese text encoder's parameters ({', '.join(mixed)}) are in neither regime: fp32 throughout, or fp16 as "
+                    "module_cross.convert_bert_weights(text_encoder) converts them (nn.Linear weights and biases fp16, embedding "
+                    "tables and LayerNorms fp32)")
+
+
+def bert_param_regime(pool_w, pool_b, proj_w, proj_b, params):
+    """bert_layout_regime of the tensors a tower call received, which must be contiguous and on the GPU."""
+    for prm in (pool_w, pool_b, proj_w, proj_b) + tuple(params):
+        if not prm.is_cuda or not prm.is_contiguous():
+            raise TypeError("the Chinese text encoder runs on contiguous CUDA parameters")
+    return bert_layout_regime(pool_w, pool_b, proj_w, proj_b, params)
+
+
+def _lin(x, w, bias):
+    if x.dtype == torch.float16:
+        return ops.gemm_f16(x, w, x.shape[0], w.shape[0], x.shape[1], bias=bias)
+    return ops.linear_f32(x, w, bias=bias)
+
+
+def _dgrad(dy, w, out=None):
+    """dy [M, N'] @ w [N', K'] (into `out`: contiguous rows of a larger buffer)."""
+    M, Np = dy.shape
+    Kp = w.shape[1]
+    if dy.dtype == torch.float16:
+        return ops.gemm_f16(dy, w, M, Kp, Np, True, False, out=out)
+    return ops.gemm_f32(dy, w, M, Kp, Np, (Np, 1), (Kp, 1), out=out)
+
+
+def _wgrad(dy, x):
+    if dy.dtype == torch.float16:
+        return ops.gemm_f16(dy, x, dy.shape[1], x.shape[1], dy.shape[0], False, False)
+    return ops.wgrad_f32(dy, x)
+
+
+def _pooler_fwd(x, w, bias, b, L):
+    return (ops.bert_pooler_f16_fwd if x.dtype == torch.float16 else ops.bert_pooler_fwd)(x, w, bias, b, L)
+
+
+def _pooler_bwd(dy, y, x, w, b, L, dx):
+    return (ops.bert_pooler_f16_bwd if x.dtype == torch.float16 else ops.bert_pooler_bwd)(dy, y, x, w, b, L, dx)
+
+
+def _bert_tower_forward(ids, mask, params, cfg, keep, dtype=torch.float32):
+    """hmmc_bert_fwd / hmmc_bert_f16_fwd: -> (last_hidden_state [b*L, D] in `dtype`, acts or None)."""
     from ._lib import call, ptr, query
     heads, inter, eps, p_hidden, p_attn, seed = cfg
     b, L = ids.shape
     vocab, D = params[0].shape
     nl = (len(params) - ops.BERT_EMB_PARAMS) // ops.BERT_LAYER_PARAMS
-    acts = torch.empty(query("hmmc_bert_act_bytes", b, L, heads, D, inter, nl, int(keep), int(p_attn > 0)), dtype=torch.uint8,
-                       device=ids.device)
-    y = torch.empty((b * L, D), dtype=torch.float32, device=ids.device)
-    call("hmmc_bert_fwd", ptr(ids), ptr(mask), ptr(y), _ptr_array(params), ptr(acts), int(keep), b, L, heads, D, inter, nl, vocab,
-         float(eps), float(p_hidden), float(p_attn), int(seed), ptr(ops.device_error_flag(ids.device)))
+    half = dtype == torch.float16
+    nbytes = (query("hmmc_bert_f16_act_bytes", b, L, heads, D, inter, nl, int(keep)) if half else
+              query("hmmc_bert_act_bytes", b, L, heads, D, inter, nl, int(keep), int(p_attn > 0)))
+    acts = torch.empty(nbytes, dtype=torch.uint8, device=ids.device)
+    y = torch.empty((b * L, D), dtype=dtype, device=ids.device)
+    call("hmmc_bert_f16_fwd" if half else "hmmc_bert_fwd", ptr(ids), ptr(mask), ptr(y), _ptr_array(params), ptr(acts), int(keep), b, L,
+         heads, D, inter, nl, vocab, float(eps), float(p_hidden), float(p_attn), int(seed), ptr(ops.device_error_flag(ids.device)))
     return y, (acts if keep else None)
 
 
 def _bert_tower_backward(dy, ids, mask, params, acts, cfg):
+    """The regime is dy's dtype (that of the forward's last_hidden_state)."""
     from ._lib import call, ptr, query
     heads, inter, eps, p_hidden, p_attn, seed = cfg
     b, L = ids.shape
     vocab, D = params[0].shape
     nl = (len(params) - ops.BERT_EMB_PARAMS) // ops.BERT_LAYER_PARAMS
+    pre = "hmmc_bert_f16" if dy.dtype == torch.float16 else "hmmc_bert"
     grads = [torch.empty_like(p) for p in params]
-    scratch = torch.empty(query("hmmc_bert_bwd_scratch_bytes", b, L, D, inter), dtype=torch.uint8, device=dy.device)
-    wsb = query("hmmc_bert_workspace_bytes", b, L, D, inter)
+    scratch = torch.empty(query(pre + "_bwd_scratch_bytes", b, L, D, inter), dtype=torch.uint8, device=dy.device)
+    wsb = query(pre + "_workspace_bytes", b, L, D, inter)
     ws = ops.workspace(wsb, dy.device, "bert")
-    call("hmmc_bert_bwd", ptr(dy), ptr(ids), ptr(mask), _ptr_array(params), _ptr_array(grads), ptr(acts), ptr(scratch), b, L, heads, D,
+    call(pre + "_bwd", ptr(dy), ptr(ids), ptr(mask), _ptr_array(params), _ptr_array(grads), ptr(acts), ptr(scratch), b, L, heads, D,
          inter, nl, vocab, params[1].shape[0], params[2].shape[0], float(p_hidden), float(p_attn), int(seed), ptr(ws), wsb)
     return grads
 
 
 class BertFn(torch.autograd.Function):
     """The Chinese text tower in one autograd node (reference modules/module_cross.py:273-277): BertModel(ids, attention_mask),
-    then text_proj of the pooler output (want = "feat" -> [b, E]) or of every hidden row (want = "hidden" -> [b, L, E]).  fp32
-    throughout.  cfg = (heads, intermediate size, LayerNorm eps, p_hidden, p_attn, seed); params: hmmc_bert_fwd's order."""
+    then text_proj of the pooler output (want = "feat" -> [b, E]) or of every hidden row (want = "hidden" -> [b, L, E]).  The
+    parameters' dtype layout selects the regime (bert_param_regime): fp32 throughout, or the fp16 kernels of csrc/bert_f16.hip
+    with fp16 pooler and text_proj; the features leave in fp32 either way.  cfg = (heads, intermediate size, LayerNorm eps,
+    p_hidden, p_attn, seed); params: hmmc_bert_fwd's order."""
 
     @staticmethod
     def forward(ctx, ids, mask, cfg, want, keep, pool_w, pool_b, proj_w, proj_b, *params):
-        for prm in (pool_w, pool_b, proj_w, proj_b) + params:
-            if prm.dtype != torch.float32 or not prm.is_cuda or not prm.is_contiguous():
-                raise TypeError("the Chinese text encoder runs in fp32 on contiguous CUDA parameters")
+        dtype = bert_param_regime(pool_w, pool_b, proj_w, proj_b, params)
         b, L = ids.shape
-        y, acts = _bert_tower_forward(ids, mask, params, cfg, keep)
+        y, acts = _bert_tower_forward(ids, mask, params, cfg, keep, dtype)
         pooled = None
         if want == "feat":
-            pooled = ops.bert_pooler_fwd(y, pool_w, pool_b, b, L)
-            out = ops.linear_f32(pooled, proj_w, bias=proj_b)
+            pooled = _pooler_fwd(y, pool_w, pool_b, b, L)
+            out = _lin(pooled, proj_w, proj_b)
         else:
-            out = ops.linear_f32(y, proj_w, bias=proj_b).view(b, L, -1)
+            out = _lin(y, proj_w, proj_b).view(b, L, -1)
         if keep:
             ctx.save_for_backward(ids, mask, y, pooled, pool_w, proj_w)
             ctx.acts, ctx.params, ctx.cfg, ctx.want = acts, params, cfg, want
-        return out
+        return ops.cast(out, torch.float32)
 
     @staticmethod
     def backward(ctx, dout):
         ids, mask, y, pooled, pool_w, proj_w = ctx.saved_tensors
         b, L = ids.shape
-        d = dout.contiguous().view(-1, dout.shape[-1])
+        d = ops.cast(dout.contiguous().view(-1, dout.shape[-1]), y.dtype)
         dproj_b = ops.colsum(d)
         dpool_w = dpool_b = None
         if ctx.want == "feat":
-            dproj_w = ops.wgrad_f32(d, pooled)
-            dpooled = ops.dgrad_f32(d, proj_w)
+            dproj_w = _wgrad(d, pooled)
+            dpooled = _dgrad(d, proj_w)
             dy = torch.zeros_like(y)                       # no gradient reaches the other rows of last_hidden_state
-            dpool_w, dpool_b = ops.bert_pooler_bwd(dpooled, pooled, y, pool_w, b, L, dy)
+            dpool_w, dpool_b = _pooler_bwd(dpooled, pooled, y, pool_w, b, L, dy)
         else:
-            dproj_w = ops.wgrad_f32(d, y)
-            dy = ops.dgrad_f32(d, proj_w)
+            dproj_w = _wgrad(d, y)
+            dy = _dgrad(d, proj_w)
         grads = _bert_tower_backward(dy, ids, mask, ctx.params, ctx.acts, ctx.cfg)
         ctx.acts = None
         return (None, None, None, None, None, dpool_w, dpool_b, dproj_w, dproj_b, *grads)
@@ -783,24 +845,22 @@ class BertManyFn(torch.autograd.Function):
     inputs' rows one after the other, padded to the longest; segs = ((row0, b, want), ...).  want = "feat": pooler + text_proj
     on the segment's class rows, addressed in place -> [b, E]; "hidden": text_proj of ALL L positions of the segment's rows
     -> [b, L, E] (the caller slices a shorter input's positions off outside this node, so the padded ones get exact zeros on
-    the way back).  The backward assembles one dy and runs one hmmc_bert_bwd: one gradient per parameter."""
+    the way back).  The backward assembles one dy and runs one hmmc_bert_bwd: one gradient per parameter.  Regimes as BertFn."""
 
     @staticmethod
     def forward(ctx, ids, mask, cfg, segs, keep, pool_w, pool_b, proj_w, proj_b, *params):
-        for prm in (pool_w, pool_b, proj_w, proj_b) + params:
-            if prm.dtype != torch.float32 or not prm.is_cuda or not prm.is_contiguous():
-                raise TypeError("the Chinese text encoder runs in fp32 on contiguous CUDA parameters")
+        dtype = bert_param_regime(pool_w, pool_b, proj_w, proj_b, params)
         R, L = ids.shape
-        y, acts = _bert_tower_forward(ids, mask, params, cfg, keep)
+        y, acts = _bert_tower_forward(ids, mask, params, cfg, keep, dtype)
         outs, pooled = [], []
         for row0, b, want in segs:
             rows = y[row0 * L:(row0 + b) * L]
             if want == "feat":
-                pooled.append(ops.bert_pooler_fwd(rows, pool_w, pool_b, b, L))
-                outs.append(ops.linear_f32(pooled[-1], proj_w, bias=proj_b))
+                pooled.append(_pooler_fwd(rows, pool_w, pool_b, b, L))
+                outs.append(ops.cast(_lin(pooled[-1], proj_w, proj_b), torch.float32))
             else:
                 pooled.append(None)
-                outs.append(ops.linear_f32(rows, proj_w, bias=proj_b).view(b, L, -1))
+                outs.append(ops.cast(_lin(rows, proj_w, proj_b), torch.float32).view(b, L, -1))
         if keep:
             ctx.save_for_backward(ids, mask, y, pool_w, proj_w, *[t for t in pooled if t is not None])
             ctx.acts, ctx.params, ctx.cfg, ctx.segs = acts, params, cfg, segs
@@ -810,7 +870,6 @@ class BertManyFn(torch.autograd.Function):
     def backward(ctx, *douts):
         ids, mask, y, pool_w, proj_w, *kept = ctx.saved_tensors
         R, L = ids.shape
-        D = y.shape[1]
         dy = torch.zeros_like(y)                           # the pooler backward writes class rows only
         acc = {}
 
@@ -818,19 +877,18 @@ class BertManyFn(torch.autograd.Function):
             acc[name] = g if name not in acc else acc[name].add_(g)
 
         for (row0, b, want), dout in zip(ctx.segs, douts):
-            d = dout.contiguous().view(-1, dout.shape[-1])
+            d = ops.cast(dout.contiguous().view(-1, dout.shape[-1]), y.dtype)
             rows, drows = y[row0 * L:(row0 + b) * L], dy[row0 * L:(row0 + b) * L]
             add("proj_b", ops.colsum(d))
             if want == "feat":
                 pooled = kept.pop(0)
-                add("proj_w", ops.wgrad_f32(d, pooled))
-                dpool_w, dpool_b = ops.bert_pooler_bwd(ops.dgrad_f32(d, proj_w), pooled, rows, pool_w, b, L, drows)
+                add("proj_w", _wgrad(d, pooled))
+                dpool_w, dpool_b = _pooler_bwd(_dgrad(d, proj_w), pooled, rows, pool_w, b, L, drows)
                 add("pool_w", dpool_w)
                 add("pool_b", dpool_b)
             else:
-                add("proj_w", ops.wgrad_f32(d, rows))
-                E = d.shape[1]
-                ops.gemm_f32(d, proj_w, b * L, D, E, (E, 1), (D, 1), out=drows)          # d @ proj_w into the segment's rows
+                add("proj_w", _wgrad(d, rows))
+                _dgrad(d, proj_w, out=drows)                                             # d @ proj_w into the segment's rows
         grads = _bert_tower_backward(dy, ids, mask, ctx.params, ctx.acts, ctx.cfg)
         ctx.acts = None
         return (None, None, None, None, None, acc.get("pool_w"), acc.get("pool_b"), acc["proj_w"], acc["proj_b"], *grads)

@@ -15,7 +15,7 @@ from torch import nn
 from . import functional as Fn
 from . import ops
 from .module_clip import dims_from_state_dict
-from .module_cross import BertLMPredictionHead, CrossConfig, TextEncoder, VisualEncoder, bert_tokenizer_constants
+from .module_cross import BertLMPredictionHead, CrossConfig, TextEncoder, VisualEncoder, bert_regime, bert_tokenizer_constants
 from .until_module import CrossEn, PreTrainedModel
 
 logger = logging.getLogger(__name__)
@@ -325,6 +325,12 @@ class BirdPreTrainedModel(CLIP4ClipPreTrainedModel):
         # MLM pass of the masked titles (the reference runs the latter after the enqueue, :413-416; the online weights do not
         # change in between and the mask's random draws are the only consumer of the host generator in this function), and the
         # two momentum passes.  The `bird` branches (unreachable from main_pretrain.py) keep separate passes.
+        if self.text_encoder.language == "chinese":
+            # the EMA walks the two encoders' parameters pairwise with the online one's dtype
+            regimes = bert_regime(self.text_encoder), bert_regime(self.text_encoder_k)
+            if regimes[0] != regimes[1]:
+                raise TypeError(f"text_encoder ({regimes[0]}) and text_encoder_k ({regimes[1]}) are in different regimes: call "
+                                "module_cross.convert_bert_weights on both or on neither")
         mlm_hidden = mlm_labels = None
         if not bird:
             mlm_ids, mlm_labels = self._mlm_inputs(title_ids)

@@ -252,6 +252,41 @@ def bert_tokenizer_constants(path):
     return out
 
 
+def _bert_linears(text_encoder):
+    """(name, module) of every nn.Linear of the Chinese branch: all of chinese_encoder.* and text_proj."""
+    out = [("chinese_encoder." + n, m) for n, m in text_encoder.chinese_encoder.named_modules() if isinstance(m, nn.Linear)]
+    return out + [("text_proj", text_encoder.text_proj)]
+
+
+def convert_bert_weights(text_encoder):
+    """Select the fp16 regime of the Chinese text encoder (csrc/bert_f16.hip), as clip.convert_weights selects the fp16 CLIP
+    towers: weight AND bias of every nn.Linear under chinese_encoder.* and of text_proj become fp16; the three embedding
+    tables and every LayerNorm weight / bias stay fp32.  In place; returns the encoder."""
+    if getattr(text_encoder, "language", None) != "chinese":
+        raise ValueError("convert_bert_weights takes a TextEncoder with language = \"chinese\"")
+    for _, m in _bert_linears(text_encoder):
+        m.weight.data = m.weight.data.half()
+        m.bias.data = m.bias.data.half()
+    return text_encoder
+
+
+def bert_regime(text_encoder):
+    """torch.float32 for the untouched layout, torch.float16 for exactly the layout convert_bert_weights produces.  Any other
+    mix of dtypes (a plain .half(), which also halves LayerNorms and embeddings; one Linear left behind) raises a TypeError
+    that names convert_bert_weights.  The decision is functional.bert_layout_regime's, the one every tower call makes."""
+    enc = text_encoder.chinese_encoder
+    return Fn.bert_layout_regime(enc.pooler.dense.weight, enc.pooler.dense.bias, text_encoder.text_proj.weight,
+                                 text_encoder.text_proj.bias, enc.flat_params())
+
+
+def _bert_max_tokens(text_encoder, L):
+    """The attention kernels' sequence limit of the encoder's regime."""
+    if L > 256:
+        raise ValueError("the masked attention kernels take at most 256 tokens")
+    if L > 64 and bert_regime(text_encoder) == torch.float16:
+        raise ValueError("the masked attention kernels take at most 64 tokens in the fp16 regime (256 in fp32)")
+
+
 class TextEncoder(nn.Module):
     """CLIP text transformer (english) or a BERT encoder + text_proj (chinese); reference modules/module_cross.py:240-305."""
 
@@ -297,8 +332,7 @@ class TextEncoder(nn.Module):
         b, L = input_ids.shape
         if L > cfg["max_position_embeddings"]:
             raise ValueError("sequence longer than the position embedding table")
-        if L > 256:
-            raise ValueError("the masked attention kernels take at most 256 tokens")
+        _bert_max_tokens(self, L)
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
         if not attention_mask.is_cuda:
@@ -385,8 +419,7 @@ def _encode_many_chinese(self, texts, wants, masks):
     Lmax = max(t.shape[1] for t in texts)
     if Lmax > cfg["max_position_embeddings"]:
         raise ValueError("sequence longer than the position embedding table")
-    if Lmax > 256:
-        raise ValueError("the masked attention kernels take at most 256 tokens")
+    _bert_max_tokens(self, Lmax)
     pad = int(self.pad_id)
     ids, ms, segs, row0 = [], [], [], 0
     for t, m, want in zip(texts, masks, wants):

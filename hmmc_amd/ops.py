@@ -913,3 +913,98 @@ def bert_pooler_bwd(dy, y, x, w, b, L, dx):
     ws = workspace(wsb, dy.device, "bert")
     call("hmmc_bert_pooler_bwd", ptr(dy), ptr(y), ptr(x), ptr(w), ptr(dz), ptr(dx), ptr(dW), ptr(db), b, L * D, D, ptr(ws), wsb)
     return dW, db
+
+
+# ---------------------------------------------------------------------------- its fp16 regime (csrc/bert_f16.hip)
+
+def masked_attention_f16_fwd(qkv, key_mask, b, L, H, p=0.0, seed=0, site=0):
+    """-> (out [b*L, 64H] fp16, lse [b, H, L] fp32); dropout on the probabilities happens inside the kernel."""
+    _chk(qkv, torch.float16, "qkv")
+    _chk(key_mask, torch.int64, "key_mask")
+    D = H * 64
+    assert tuple(qkv.shape) == (b * L, 3 * D) and tuple(key_mask.shape) == (b, L)
+    out = torch.empty((b * L, D), dtype=torch.float16, device=qkv.device)
+    lse = torch.empty((b, H, L), dtype=torch.float32, device=qkv.device)
+    call("hmmc_masked_attention_f16_fwd", ptr(qkv), ptr(key_mask), ptr(out), ptr(lse), b, L, H, float(p), int(seed), int(site))
+    return out, lse
+
+
+def masked_attention_f16_bwd(qkv, key_mask, lse, dout, b, L, H, p=0.0, seed=0, site=0, want_dbias=False):
+    _chk(dout, torch.float16, "dout")
+    _chk(lse, torch.float32, "lse")
+    assert tuple(dout.shape) == (b * L, H * 64)
+    dqkv = torch.empty_like(qkv)
+    dbias = torch.empty((b, 3 * H * 64), dtype=torch.float32, device=qkv.device) if want_dbias else None
+    call("hmmc_masked_attention_f16_bwd", ptr(qkv), ptr(key_mask), ptr(lse), ptr(dout), ptr(dqkv), ptr(dbias), b, L, H, float(p),
+         int(seed), int(site))
+    return (dqkv, dbias) if want_dbias else dqkv
+
+
+def gelu_erf_f16_fwd(x, out=None):
+    _chk(x, torch.float16, "x")
+    y = out if out is not None else torch.empty_like(x)
+    call("hmmc_gelu_erf_f16_fwd", ptr(x), ptr(y), x.numel())
+    return y
+
+
+def gelu_erf_f16_bwd(x, dy):
+    _chk(x, torch.float16, "x")
+    _chk(dy, torch.float16, "dy")
+    dx = torch.empty_like(x)
+    call("hmmc_gelu_erf_f16_bwd", ptr(x), ptr(dy), ptr(dx), x.numel())
+    return dx
+
+
+def dropout_f16_fwd(x, p, seed, site, resid=None, out=None):
+    """fp16 twin of dropout_fwd: y = fp16(x o keep / (1 - p) + resid), the same keep function of (seed, site, element index)."""
+    _chk(x, torch.float16, "x")
+    if resid is not None:
+        _chk(resid, torch.float16, "resid")
+        assert resid.numel() == x.numel()
+    y = out if out is not None else torch.empty_like(x)
+    call("hmmc_dropout_f16_fwd", ptr(x), ptr(resid), ptr(y), x.numel(), float(p), int(seed), int(site))
+    return y
+
+
+def dropout_f16_bwd(dy, p, seed, site):
+    _chk(dy, torch.float16, "dy")
+    dx = torch.empty_like(dy)
+    call("hmmc_dropout_f16_bwd", ptr(dy), ptr(dx), dy.numel(), float(p), int(seed), int(site))
+    return dx
+
+
+def bert_pooler_f16_fwd(x, w, bias, b, L):
+    """fp16(tanh(fp16(x[class rows] @ w.T + bias))): x [b*L, D] -> [b, D]."""
+    for t, n in ((x, "x"), (w, "w"), (bias, "bias")):
+        _chk(t, torch.float16, n)
+    D = w.shape[0]
+    assert tuple(x.shape) == (b * L, D) and tuple(w.shape) == (D, D)
+    y = torch.empty((b, D), dtype=torch.float16, device=x.device)
+    call("hmmc_bert_pooler_f16_fwd", ptr(x), ptr(w), ptr(bias), ptr(y), b, L * D, D)
+    return y
+
+
+def bert_pooler_f16_bwd(dy, y, x, w, b, L, dx):
+    """dx [b*L, D]: its class rows receive the data gradient, the others are left as they are.  -> (dW, db)."""
+    _chk(dy, torch.float16, "dy")
+    _chk(dx, torch.float16, "dx")
+    D = w.shape[0]
+    assert tuple(dy.shape) == (b, D) and tuple(dx.shape) == (b * L, D)
+    dz = torch.empty_like(dy)
+    dW = torch.empty_like(w)
+    db = torch.empty(D, dtype=torch.float16, device=dy.device)
+    wsb = query("hmmc_bert_pooler_f16_bwd_workspace", b, D)
+    ws = workspace(wsb, dy.device, "bert")
+    call("hmmc_bert_pooler_f16_bwd", ptr(dy), ptr(y), ptr(x), ptr(w), ptr(dz), ptr(dx), ptr(dW), ptr(db), b, L * D, D, ptr(ws), wsb)
+    return dW, db
+
+
+def cast(x, dtype):
+    """fp16 <-> fp32 (hmmc_cast)."""
+    if x.dtype == dtype:
+        return x
+    _chk(x, torch.float32 if dtype == torch.float16 else torch.float16, "x")
+    y = torch.empty(x.shape, dtype=dtype, device=x.device)
+    if x.numel():
+        call("hmmc_cast", ptr(x), ptr(y), x.numel(), 1 if dtype == torch.float16 else 0)
+    return y

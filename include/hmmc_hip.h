@@ -385,7 +385,7 @@ int hmmc_mlm_mask(const long* ids, const unsigned char* masked, const unsigned c
                   hmmc_stream_t stream);
 
 /* ---- The Chinese text branch (language = "chinese", modules/module_cross.py:257-265,273-277): a HuggingFace BertModel, post-LN,
- * erf-GELU, LayerNorm eps 1e-12, all fp32 (hmmc_gemm_f32 for every GEMM, nothing rounded to fp16).
+ * erf-GELU, LayerNorm eps 1e-12.  The fp32 regime first: hmmc_gemm_f32 for every GEMM, nothing rounded to fp16.
  *
  * Dropout (BertEmbeddings / BertSelfAttention / BertSelfOutput / BertOutput in train mode).  One counter-based generator,
  * Philox4x32-10: element idx of site `site` is kept iff word (idx & 3) of Philox(key = seed, counter = (idx >> 2, site)) is
@@ -451,6 +451,53 @@ int hmmc_bert_fwd(const long* ids, const long* key_mask, float* y, const void* c
 int hmmc_bert_bwd(const float* dy, const long* ids, const long* key_mask, const void* const* params, void* const* grads,
                   const void* acts, void* scratch, int nseq, int L, int heads, int D, int inter, int nlayers, long vocab, int max_pos,
                   int type_vocab, float p_hidden, float p_attn, long seed, void* workspace, size_t ws_bytes, hmmc_stream_t stream);
+
+/* ---- The fp16 regime of the same encoder (modules/module_cross.py:257-265,273-277 again; the reference has no recipe for a half
+ * Chinese encoder, so the regime mirrors what convert_weights, modules/module_clip.py:506-527, does to the CLIP towers): every
+ * nn.Linear weight and bias is fp16, the three embedding tables and every LayerNorm parameter stay fp32.  Embedding, its
+ * LayerNorm and dropout site 0 run on the fp32 entry points above, followed by one hmmc_cast; from there the residual stream and
+ * every saved activation are fp16, every GEMM is hmmc_gemm_f16, LayerNorm is dtype 0 with the config's eps.  The rounding points
+ * are listed at the top of csrc/bert_f16.hip.
+ *
+ * Key-masked fp16 MFMA attention, head dim 64, 1 <= L <= 64 (L > 64: HMMC_ERR_UNSUPPORTED), the contract of
+ * hmmc_masked_attention_fwd: key_mask int64 [b, L], nonzero = valid key, any pattern; masked keys get probability exactly 0 and
+ * their K / V rows are never used, whatever bits they hold; every query row is computed; a sequence without any valid key is
+ * outside the contract.  Flash-style: the forward saves lse [b, H, L] (fp32) only and no [b, H, L, L] tensor exists in either
+ * direction; dropout on the probabilities is applied in the kernel and regenerated by the backward, element index
+ * ((n*H + h)*L + i)*64 + j (a row pitch of 64 whatever L is); p == 0 takes instantiations without dropout code.  The softmax is
+ * fp32; Pd = fp16(P o keep / (1 - p)) multiplies V and dO, dS = fp16(P o (dP - delta) / 8) multiplies K and Q.  Backward: dqkv
+ * is written whole, dK / dV rows of masked keys are exactly 0; dbias_partial (optional) as hmmc_attention_f16_bwd. */
+int hmmc_masked_attention_f16_fwd(const void* qkv, const long* key_mask, void* out, float* lse, int b, int L, int H, float p,
+                                  long seed, int site, hmmc_stream_t stream);
+int hmmc_masked_attention_f16_bwd(const void* qkv, const long* key_mask, const float* lse, const void* dout, void* dqkv,
+                                  float* dbias_partial, int b, int L, int H, float p, long seed, int site, hmmc_stream_t stream);
+/* erf-GELU of BertIntermediate on fp16 tensors: y = fp16(gelu(x)), dx = fp16(dy gelu'(x)), fp32 erf; n % 8 == 0, 16-byte aligned. */
+int hmmc_gelu_erf_f16_fwd(const void* x, void* y, long n, hmmc_stream_t stream);
+int hmmc_gelu_erf_f16_bwd(const void* x, const void* dy, void* dx, long n, hmmc_stream_t stream);
+/* hmmc_dropout_fwd / _bwd on fp16 tensors: y = fp16(x o keep / (1 - p) + resid) with the SAME keep function of (seed, site,
+ * element index); y may alias x; n % 8 == 0, 16-byte aligned.  p = 0 without resid passes the values through bit for bit. */
+int hmmc_dropout_f16_fwd(const void* x, const void* resid, void* y, long n, float p, long seed, int site, hmmc_stream_t stream);
+int hmmc_dropout_f16_bwd(const void* dy, void* dx, long n, float p, long seed, int site, hmmc_stream_t stream);
+/* BertPooler on fp16 tensors, the class rows addressed in place as in hmmc_bert_pooler_fwd: z = fp16(x W^T + bias) (hmmc_gemm_f16),
+ * y = fp16(tanh(z)).  Backward: dz [b, D] (scratch) = fp16(dy (1 - y^2)); dW, db written; dx receives dz W at the class rows
+ * only.  D % 64 == 0, stride % 8 == 0; workspace: hmmc_bert_pooler_f16_bwd_workspace bytes. */
+int hmmc_bert_pooler_f16_fwd(const void* x, const void* W, const void* bias, void* y, int b, long stride, int D, hmmc_stream_t stream);
+size_t hmmc_bert_pooler_f16_bwd_workspace(int b, int D);
+int hmmc_bert_pooler_f16_bwd(const void* dy, const void* y, const void* x, const void* W, void* dz, void* dx, void* dW, void* db,
+                             int b, long stride, int D, void* workspace, size_t ws_bytes, hmmc_stream_t stream);
+/* Tower runtime of the fp16 regime: hmmc_bert_fwd's parameter order, site numbering, keep_acts meaning and p == 0 shortcuts;
+ * params / grads hold fp32 pointers for the 5 embedding entries and every LayerNorm weight / bias, fp16 pointers for every
+ * dense weight / bias.  y and dy [nseq*L, D] are fp16.  grads are written, not accumulated.  L <= 64, D = 64 * heads <= 1024,
+ * inter % 64 == 0; anything else returns HMMC_ERR_UNSUPPORTED before any launch. */
+size_t hmmc_bert_f16_act_bytes(int nseq, int L, int heads, int D, int inter, int nlayers, int keep_acts);
+size_t hmmc_bert_f16_bwd_scratch_bytes(int nseq, int L, int D, int inter);
+size_t hmmc_bert_f16_workspace_bytes(int nseq, int L, int D, int inter);
+int hmmc_bert_f16_fwd(const long* ids, const long* key_mask, void* y, const void* const* params, void* acts, int keep_acts, int nseq,
+                      int L, int heads, int D, int inter, int nlayers, long vocab, float eps, float p_hidden, float p_attn, long seed,
+                      int* err_flag, hmmc_stream_t stream);
+int hmmc_bert_f16_bwd(const void* dy, const long* ids, const long* key_mask, const void* const* params, void* const* grads,
+                      const void* acts, void* scratch, int nseq, int L, int heads, int D, int inter, int nlayers, long vocab, int max_pos,
+                      int type_vocab, float p_hidden, float p_attn, long seed, void* workspace, size_t ws_bytes, hmmc_stream_t stream);
 
 /* Native layer runtime: all ResidualAttentionBlocks of a tower in one call (modules/module_clip.py:231-268 fp16 CLIP
  * towers, fp32 = 0, eps 1e-5; modules/module_cross.py:114-149 fp32 temporal transformer, fp32 = 1, eps 1e-12).

@@ -4,8 +4,8 @@
 // kernels of bert_f32.hip, followed by ONE cast; from there the residual stream and every saved activation are fp16.  GEMMs:
 // hmmc_gemm_f16 (fp32 accumulation, bias / residual in the epilogue); LayerNorm and reductions: the fp16 kernels of
 // norm_elem.hip with fp32 statistics.  New kernels here: key-masked MFMA attention with in-kernel dropout, erf-GELU, dropout
-// and the pooler's tanh on fp16 tensors; hmmc_bert_f16_fwd / hmmc_bert_f16_bwd only SEQUENCE kernels of this library on the
-// caller's stream.  No atomics, fixed summation order: bit-identical from run to run.
+// and the pooler's tanh on fp16 tensors; hmmc_bert_f16_fwd / hmmc_bert_f16_bwd are the one sequence of bert_tower.hip with
+// f32 = false.  No atomics, fixed summation order: bit-identical from run to run.
 //
 // ROUNDING POINTS (tests/bert16_ref.py restates exactly these; everything between two of them is fp32):
 //   x0 = fp16(dropout_0(LN(word + pos + type)))                         one cast after the fp32 embedding kernels
@@ -21,6 +21,7 @@
 //   pooler: z = fp16(x W^T + b) (the GEMM), y = fp16(tanh(z)); dz = fp16(dy (1 - y^2))
 //   bias gradients: fp32 column sums of the fp16 gradient, rounded once; weight gradients: fp16(fp32 sums)
 #include "attn_common.h"
+#include "bert_regime.h"
 #include "philox.h"
 #include <algorithm>
 
@@ -395,73 +396,9 @@ __global__ __launch_bounds__(256) void tanh16_bwd_kernel(const half_t* __restric
   }
 }
 
-// y[M,N] = x[M,K] w[N,K]^T + bias (+ resid);  lda / ldc: row strides of x and y (0 = dense)
-inline int linear16(const void* x, const void* w, void* y, int M, int N, int K, const void* bias, const void* resid, hipStream_t s,
-                    int lda = 0, int ldc = 0) {
-  return hmmc_gemm_f16(x, w, y, M, N, K, lda ? lda : K, K, ldc ? ldc : N, 1, 1, bias, resid, nullptr, nullptr,
-                       (bias ? EPI_BIAS : 0) | (resid ? EPI_RESID : 0), nullptr, 0, s);
-}
-// dx[M,K'] = dy[M,N'] w[N',K'] (+ resid);  ldy / ldx: row strides of dy and dx (0 = dense)
-inline int dgrad16(const void* dy, const void* w, void* dx, int M, int Np, int Kp, const void* resid, hipStream_t s, int ldy = 0,
-                   int ldx = 0) {
-  return hmmc_gemm_f16(dy, w, dx, M, Kp, Np, ldy ? ldy : Np, Kp, ldx ? ldx : Kp, 1, 0, nullptr, resid, nullptr, nullptr,
-                       resid ? EPI_RESID : 0, nullptr, 0, s);
-}
-// dW[N',K'] = dy[T,N']^T x[T,K'];  ldy / ldx: row strides of dy and x (0 = dense); split over T where the workspace allows
-inline int wgrad16(const void* dy, const void* x, void* dw, int T, int Np, int Kp, void* ws, size_t wsb, hipStream_t s, int ldy = 0,
-                   int ldx = 0) {
-  const size_t need = hmmc_gemm_f16_workspace(Np, Kp, T);
-  return hmmc_gemm_f16(dy, x, dw, Np, Kp, T, ldy ? ldy : Np, ldx ? ldx : Kp, Kp, 0, 0, nullptr, nullptr, nullptr, nullptr, 0,
-                       need <= wsb ? ws : nullptr, need <= wsb ? wsb : 0, s);
-}
-
-// activation layout of hmmc_bert_f16_fwd / hmmc_bert_f16_bwd: the fp32 embedding rows (pre-LayerNorm e, statistics, the
-// LayerNorm's output before the cast), then one fp16 slab per layer (keep_acts) or one slab that every layer reuses
-struct Emb16 { float *e, *mean, *rstd, *x0; size_t bytes; };
-struct Layer16 { half_t *x, *qkv, *att, *pre1, *x1, *h, *g, *pre2; float *lse, *m1, *r1, *m2, *r2; size_t bytes; };
-Emb16 carve_emb16(char* base, long T, int D) {
-  Emb16 a;
-  char* p = base;
-  a.e = (float*)p; p += al((size_t)T * D * 4);
-  a.mean = (float*)p; p += al((size_t)T * 4);
-  a.rstd = (float*)p; p += al((size_t)T * 4);
-  a.x0 = (float*)p; p += al((size_t)T * D * 4);
-  a.bytes = (size_t)(p - base);
-  return a;
-}
-Layer16 carve_layer16(char* base, long T, int D, int I, int H) {
-  Layer16 a;
-  const size_t td = al((size_t)T * D * 2), ti = al((size_t)T * I * 2), tr = al((size_t)T * 4);
-  char* p = base;
-  a.x = (half_t*)p; p += td;
-  a.qkv = (half_t*)p; p += al((size_t)T * 3 * D * 2);
-  a.att = (half_t*)p; p += td;
-  a.pre1 = (half_t*)p; p += td;
-  a.x1 = (half_t*)p; p += td;
-  a.h = (half_t*)p; p += ti;
-  a.g = (half_t*)p; p += ti;
-  a.pre2 = (half_t*)p; p += td;
-  a.lse = (float*)p; p += al((size_t)T * H * 4);
-  a.m1 = (float*)p; p += tr;
-  a.r1 = (float*)p; p += tr;
-  a.m2 = (float*)p; p += tr;
-  a.r2 = (float*)p; p += tr;
-  a.bytes = (size_t)(p - base);
-  return a;
-}
-
-constexpr int B16_EMB_PARAMS = 5, B16_LAYER_PARAMS = 16;
-// HMMC_OK, or why this regime does not take the shape (checked before any launch)
-inline int bert16_shape(int nseq, int L, int heads, int D, int inter, int nlayers) {
-  if (nseq <= 0 || L <= 0 || heads <= 0 || nlayers <= 0 || inter <= 0 || D != heads * 64) return HMMC_ERR_ARG;
-  if (L > 64 || D > 1024 || (inter & 63)) return HMMC_ERR_UNSUPPORTED;        // a k-major GEMM operand takes whole 64-wide K tiles
-  if ((long)nseq * L * std::max(3 * D, inter) > 0x7fffffffL) return HMMC_ERR_UNSUPPORTED;
-  return HMMC_OK;
-}
-
 int mattn16_args_ok(const void* qkv, const long* mask, int b, int L, int H, float p) {
-  if (!qkv || !mask || b <= 0 || L <= 0 || H <= 0 || !(p >= 0.f) || !(p < 1.f)) return HMMC_ERR_ARG;
-  if (L > 64 || (long)b * L * 3 * DH * H > 0x7fffffffL) return HMMC_ERR_UNSUPPORTED;
+  if (!qkv || !mask || b <= 0 || L <= 0 || H <= 0 || !drop_p_ok(p)) return HMMC_ERR_ARG;
+  if (L > MATTN_F16_MAXL || (long)b * L * 3 * DH * H > 0x7fffffffL) return HMMC_ERR_UNSUPPORTED;
   return HMMC_OK;
 }
 
@@ -526,7 +463,7 @@ extern "C" int hmmc_gelu_erf_f16_bwd(const void* x, const void* dy, void* dx, lo
 
 extern "C" int hmmc_dropout_f16_fwd(const void* x, const void* resid, void* y, long n, float p, long seed, int site,
                                     hipStream_t stream) {
-  if (!x || !y || n <= 0 || !(p >= 0.f) || !(p < 1.f)) return HMMC_ERR_ARG;
+  if (!x || !y || n <= 0 || !drop_p_ok(p)) return HMMC_ERR_ARG;
   if ((n & 7) || (((uintptr_t)x | (uintptr_t)y | (uintptr_t)resid) & 15)) return HMMC_ERR_UNSUPPORTED;
   if (p == 0.f) {
     if (!resid) {
@@ -545,168 +482,11 @@ extern "C" int hmmc_dropout_f16_bwd(const void* dy, void* dx, long n, float p, l
   return hmmc_dropout_f16_fwd(dy, nullptr, dx, n, p, seed, site, stream);
 }
 
-extern "C" int hmmc_bert_pooler_f16_fwd(const void* x, const void* W, const void* bias, void* y, int b, long stride, int D,
-                                        hipStream_t stream) {
-  if (!x || !W || !bias || !y || b <= 0 || D <= 0 || stride < D) return HMMC_ERR_ARG;
-  if (stride > 0x7fffffffL) return HMMC_ERR_UNSUPPORTED;
-  CK(linear16(x, W, y, b, D, D, bias, nullptr, stream, (int)stride, 0));
-  hipLaunchKernelGGL(tanh16_kernel, dim3(nblk((long)b * D)), dim3(256), 0, stream, (half_t*)y, (long)b * D);
+int bert_tanh_f16(void* y, long n, hipStream_t s) {
+  hipLaunchKernelGGL(tanh16_kernel, dim3(nblk(n)), dim3(256), 0, s, (half_t*)y, n);
   return hmmc_launch_status();
 }
-
-extern "C" size_t hmmc_bert_pooler_f16_bwd_workspace(int b, int D) {
-  return al(std::max(hmmc_colsum_workspace(b, D), hmmc_gemm_f16_workspace(D, D, b)));
-}
-
-extern "C" int hmmc_bert_pooler_f16_bwd(const void* dy, const void* y, const void* x, const void* W, void* dz, void* dx, void* dW,
-                                        void* db, int b, long stride, int D, void* workspace, size_t ws_bytes, hipStream_t stream) {
-  if (!dy || !y || !x || !W || !dz || !dx || !dW || !db || b <= 0 || D <= 0 || stride < D) return HMMC_ERR_ARG;
-  if (stride > 0x7fffffffL) return HMMC_ERR_UNSUPPORTED;
-  if (!workspace || ws_bytes < hmmc_bert_pooler_f16_bwd_workspace(b, D)) return HMMC_ERR_WORKSPACE;
-  hipLaunchKernelGGL(tanh16_bwd_kernel, dim3(nblk((long)b * D)), dim3(256), 0, stream, (const half_t*)dy, (const half_t*)y, (half_t*)dz,
-                     (long)b * D);
-  CK(hmmc_launch_status());
-  CK(hmmc_colsum(dz, db, b, D, D, 0, 0, 0, workspace, ws_bytes, stream));
-  CK(wgrad16(dz, x, dW, b, D, D, workspace, ws_bytes, stream, 0, (int)stride));
-  return dgrad16(dz, W, dx, b, D, D, nullptr, stream, 0, (int)stride);
-}
-
-extern "C" size_t hmmc_bert_f16_act_bytes(int nseq, int L, int heads, int D, int inter, int nlayers, int keep_acts) {
-  const long T = (long)nseq * L;
-  return carve_emb16(nullptr, T, D).bytes + carve_layer16(nullptr, T, D, inter, heads).bytes * (size_t)(keep_acts ? nlayers : 1);
-}
-// transient gradients of the backward: six fp16 [T, D], two [T, inter], one [T, 3D], and two fp32 [T, D] for the embedding
-extern "C" size_t hmmc_bert_f16_bwd_scratch_bytes(int nseq, int L, int D, int inter) {
-  const long T = (long)nseq * L;
-  return 6 * al((size_t)T * D * 2) + 2 * al((size_t)T * inter * 2) + al((size_t)T * 3 * D * 2) + 2 * al((size_t)T * D * 4);
-}
-extern "C" size_t hmmc_bert_f16_workspace_bytes(int nseq, int L, int D, int inter) {
-  if (nseq <= 0 || L <= 0 || D <= 0 || inter <= 0 || (long)nseq * L * std::max(3 * D, inter) > 0x7fffffffL) return 0;   // shapes the tower refuses
-  const int T = nseq * L;
-  size_t w = std::max(hmmc_layernorm_bwd_workspace(T, D), hmmc_colsum_workspace(T, inter));
-  w = std::max(w, hmmc_colsum_workspace(T, D));
-  w = std::max(w, hmmc_bert_embed_bwd_workspace(T, L, D));
-  const int NK[3][2] = {{D, D}, {D, inter}, {inter, D}};
-  for (const auto& nk : NK) w = std::max(w, hmmc_gemm_f16_workspace(nk[0], nk[1], T));
-  return al(w);
-}
-
-extern "C" int hmmc_bert_f16_fwd(const long* ids, const long* key_mask, void* y, const void* const* params, void* acts, int keep_acts,
-                                 int nseq, int L, int heads, int D, int inter, int nlayers, long vocab, float eps, float p_hidden,
-                                 float p_attn, long seed, int* err_flag, hipStream_t s) {
-  if (!ids || !key_mask || !y || !params || !acts || vocab <= 0) return HMMC_ERR_ARG;
-  if (!(p_hidden >= 0.f) || !(p_hidden < 1.f) || !(p_attn >= 0.f) || !(p_attn < 1.f)) return HMMC_ERR_ARG;
-  CK(bert16_shape(nseq, L, heads, D, inter, nlayers));
-  const long T = (long)nseq * L;
-  const Emb16 ea = carve_emb16((char*)acts, T, D);
-  char* const slabs = (char*)acts + ea.bytes;
-  const size_t slab = carve_layer16(nullptr, T, D, inter, heads).bytes;
-  Layer16 a = carve_layer16(slabs, T, D, inter, heads);
-  // x0 = fp16(dropout(LN(word + pos + type 0))): the fp32 kernels, then one cast into the first slab's input
-  const float* const* E = (const float* const*)params;
-  CK(hmmc_bert_embed_fwd(ids, E[0], E[1], E[2], E[3], E[4], keep_acts ? ea.e : nullptr, ea.x0, ea.mean, ea.rstd, T, L, D, vocab, eps,
-                         err_flag, s));
-  CK(hmmc_dropout_fwd(ea.x0, nullptr, ea.x0, T * D, p_hidden, seed, 0, s));
-  CK(hmmc_cast(ea.x0, a.x, T * D, 1, s));
-  for (int i = 0; i < nlayers; ++i) {
-    const void* const* W = params + B16_EMB_PARAMS + (size_t)i * B16_LAYER_PARAMS;
-    if (keep_acts) a = carve_layer16(slabs + (size_t)i * slab, T, D, inter, heads);
-    // the layer's output: the next slab's input, y for the last layer; without kept activations the one slab's input slot,
-    // which is dead once attention.output.dense (or its dropout) has read it as the residual
-    half_t* out = i + 1 == nlayers ? (half_t*)y : keep_acts ? carve_layer16(slabs + (size_t)(i + 1) * slab, T, D, inter, heads).x : a.x;
-    for (int j = 0; j < 3; ++j)                                    // query | key | value into one [T, 3D] buffer
-      CK(linear16(a.x, W[2 * j], a.qkv + (size_t)j * D, (int)T, D, D, W[2 * j + 1], nullptr, s, 0, 3 * D));
-    CK(hmmc_masked_attention_f16_fwd(a.qkv, key_mask, a.att, a.lse, nseq, L, heads, p_attn, seed, 1 + 3 * i, s));
-    if (p_hidden > 0.f) {
-      CK(linear16(a.att, W[6], a.pre1, (int)T, D, D, W[7], nullptr, s));
-      CK(hmmc_dropout_f16_fwd(a.pre1, a.x, a.pre1, T * D, p_hidden, seed, 2 + 3 * i, s));
-    } else {
-      CK(linear16(a.att, W[6], a.pre1, (int)T, D, D, W[7], a.x, s));
-    }
-    CK(hmmc_layernorm_fwd(a.pre1, (const float*)W[8], (const float*)W[9], a.x1, a.m1, a.r1, nullptr, (int)T, D, D, eps, 0, s));
-    CK(linear16(a.x1, W[10], a.h, (int)T, inter, D, W[11], nullptr, s));
-    CK(hmmc_gelu_erf_f16_fwd(a.h, a.g, T * inter, s));
-    if (p_hidden > 0.f) {
-      CK(linear16(a.g, W[12], a.pre2, (int)T, D, inter, W[13], nullptr, s));
-      CK(hmmc_dropout_f16_fwd(a.pre2, a.x1, a.pre2, T * D, p_hidden, seed, 3 + 3 * i, s));
-    } else {
-      CK(linear16(a.g, W[12], a.pre2, (int)T, D, inter, W[13], a.x1, s));
-    }
-    CK(hmmc_layernorm_fwd(a.pre2, (const float*)W[14], (const float*)W[15], out, a.m2, a.r2, nullptr, (int)T, D, D, eps, 0, s));
-  }
-  return HMMC_OK;
-}
-
-extern "C" int hmmc_bert_f16_bwd(const void* dy, const long* ids, const long* key_mask, const void* const* params, void* const* grads,
-                                 const void* acts, void* scratch, int nseq, int L, int heads, int D, int inter, int nlayers,
-                                 long vocab, int max_pos, int type_vocab, float p_hidden, float p_attn, long seed, void* workspace,
-                                 size_t ws_bytes, hipStream_t s) {
-  if (!dy || !ids || !key_mask || !params || !grads || !acts || !scratch || vocab <= 0) return HMMC_ERR_ARG;
-  if (!(p_hidden >= 0.f) || !(p_hidden < 1.f) || !(p_attn >= 0.f) || !(p_attn < 1.f) || max_pos < L || type_vocab <= 0) return HMMC_ERR_ARG;
-  CK(bert16_shape(nseq, L, heads, D, inter, nlayers));
-  if (!workspace || ws_bytes < hmmc_bert_f16_workspace_bytes(nseq, L, D, inter)) return HMMC_ERR_WORKSPACE;
-  const long T = (long)nseq * L;
-  const bool hdrop = p_hidden > 0.f;
-  const Emb16 ea = carve_emb16((char*)acts, T, D);
-  char* const slabs = (char*)acts + ea.bytes;
-  const size_t slab = carve_layer16(nullptr, T, D, inter, heads).bytes;
-  char* sp = (char*)scratch;
-  half_t* td[6];
-  for (auto& t : td) { t = (half_t*)sp; sp += al((size_t)T * D * 2); }
-  half_t* const dA = td[0]; half_t* const dB = td[1]; half_t* const dC = td[2]; half_t* const dD = td[3];
-  half_t* const dg = (half_t*)sp; sp += al((size_t)T * inter * 2);
-  half_t* const dh = (half_t*)sp; sp += al((size_t)T * inter * 2);
-  half_t* const dqkv = (half_t*)sp; sp += al((size_t)T * 3 * D * 2);
-  float* const dx0 = (float*)sp; sp += al((size_t)T * D * 4);
-  float* const de = (float*)sp;
-  const half_t* g_in = (const half_t*)dy;
-  for (int i = nlayers - 1; i >= 0; --i) {
-    const void* const* W = params + B16_EMB_PARAMS + (size_t)i * B16_LAYER_PARAMS;
-    void* const* GW = grads + B16_EMB_PARAMS + (size_t)i * B16_LAYER_PARAMS;
-    const Layer16 a = carve_layer16(slabs + (size_t)i * slab, T, D, inter, heads);
-    half_t* const g_out = td[4 + (i & 1)];
-    // ---- out = LN(pre2), pre2 = dropout(g W_o^T + b_o) + x1: dA = d(pre2); without dropout its column sums are d(b_o)
-    CK(hmmc_layernorm_bwd(g_in, a.pre2, (const float*)W[14], a.m2, a.r2, nullptr, dA, (float*)GW[14], (float*)GW[15],
-                          hdrop ? nullptr : GW[13], nullptr, (int)T, D, D, 0, workspace, ws_bytes, s));
-    const half_t* da2 = dA;
-    if (hdrop) {
-      CK(hmmc_dropout_f16_bwd(dA, dB, T * D, p_hidden, seed, 3 + 3 * i, s));
-      CK(hmmc_colsum(dB, GW[13], (int)T, D, D, 0, 0, 0, workspace, ws_bytes, s));
-      da2 = dB;
-    }
-    CK(wgrad16(da2, a.g, GW[12], (int)T, D, inter, workspace, ws_bytes, s));
-    CK(dgrad16(da2, W[12], dg, (int)T, D, inter, nullptr, s));
-    CK(hmmc_gelu_erf_f16_bwd(a.h, dg, dh, T * inter, s));
-    CK(hmmc_colsum(dh, GW[11], (int)T, inter, inter, 0, 0, 0, workspace, ws_bytes, s));
-    CK(wgrad16(dh, a.x1, GW[10], (int)T, inter, D, workspace, ws_bytes, s));
-    CK(dgrad16(dh, W[10], dC, (int)T, inter, D, dA, s));                // d(x1): through intermediate.dense and the residual
-    // ---- x1 = LN(pre1), pre1 = dropout(att W_ao^T + b_ao) + x: dD = d(pre1)
-    CK(hmmc_layernorm_bwd(dC, a.pre1, (const float*)W[8], a.m1, a.r1, nullptr, dD, (float*)GW[8], (float*)GW[9],
-                          hdrop ? nullptr : GW[7], nullptr, (int)T, D, D, 0, workspace, ws_bytes, s));
-    const half_t* da1 = dD;
-    if (hdrop) {
-      CK(hmmc_dropout_f16_bwd(dD, dB, T * D, p_hidden, seed, 2 + 3 * i, s));
-      CK(hmmc_colsum(dB, GW[7], (int)T, D, D, 0, 0, 0, workspace, ws_bytes, s));
-      da1 = dB;
-    }
-    CK(wgrad16(da1, a.att, GW[6], (int)T, D, D, workspace, ws_bytes, s));
-    CK(dgrad16(da1, W[6], dA, (int)T, D, D, nullptr, s));               // d(att)
-    CK(hmmc_masked_attention_f16_bwd(a.qkv, key_mask, a.lse, dA, dqkv, nullptr, nseq, L, heads, p_attn, seed, 1 + 3 * i, s));
-    for (int j = 0; j < 3; ++j) {
-      CK(hmmc_colsum(dqkv + (size_t)j * D, GW[2 * j + 1], (int)T, D, 3 * D, 0, 0, 0, workspace, ws_bytes, s));
-      CK(wgrad16(dqkv + (size_t)j * D, a.x, GW[2 * j], (int)T, D, D, workspace, ws_bytes, s, 3 * D, 0));
-    }
-    // d(x) = dq W_q + dk W_k + dv W_v + d(pre1), added in this order
-    CK(dgrad16(dqkv, W[0], dC, (int)T, D, D, dD, s, 3 * D));
-    CK(dgrad16(dqkv + D, W[2], dA, (int)T, D, D, dC, s, 3 * D));
-    CK(dgrad16(dqkv + 2 * (size_t)D, W[4], g_out, (int)T, D, D, dA, s, 3 * D));
-    g_in = g_out;
-  }
-  // ---- x0 = fp16(dropout(LN(e))): back to fp32 for the embedding tables and the embedding LayerNorm
-  const float* const* E = (const float* const*)params;
-  float* const* G = (float* const*)grads;
-  CK(hmmc_cast(g_in, dx0, T * D, 0, s));
-  CK(hmmc_dropout_bwd(dx0, dx0, T * D, p_hidden, seed, 0, s));
-  return hmmc_bert_embed_bwd(ids, dx0, ea.e, E[3], ea.mean, ea.rstd, de, G[0], G[1], G[2], G[3], G[4], T, L, D, vocab, max_pos, type_vocab,
-                             workspace, ws_bytes, s);
+int bert_tanh_bwd_f16(const void* dy, const void* y, void* dz, long n, hipStream_t s) {
+  hipLaunchKernelGGL(tanh16_bwd_kernel, dim3(nblk(n)), dim3(256), 0, s, (const half_t*)dy, (const half_t*)y, (half_t*)dz, n);
+  return hmmc_launch_status();
 }

@@ -3,9 +3,10 @@
 // LayerNorm, dense + erf-GELU, dense + residual + LayerNorm], tanh pooler; dropout after the embedding LayerNorm, on the
 // attention probabilities and after both output projections).  Everything is fp32: the GEMMs are hmmc_gemm_f32 (exact f32
 // MFMA), nothing is rounded to fp16.  New kernels here: embedding + LayerNorm in one pass, key-masked attention with
-// dropout on the probabilities, counter-based dropout, the pooler's tanh; hmmc_bert_fwd / hmmc_bert_bwd only SEQUENCE
-// kernels of this library on the caller's stream.  No atomics, fixed summation order: bit-identical from run to run.
-#include "common.h"
+// dropout on the probabilities, counter-based dropout, the pooler's tanh; bert_tower.hip SEQUENCES them, and the fp16
+// regime's kernels of bert_f16.hip, behind hmmc_bert_fwd / hmmc_bert_bwd.  No atomics, fixed summation order: bit-identical
+// from run to run.
+#include "bert_regime.h"
 #include "philox.h"
 #include <algorithm>
 
@@ -214,7 +215,7 @@ __global__ __launch_bounds__(64) void mattn_bwd_kernel(const float* __restrict__
 }
 
 // 65 <= L <= 256: one 256-thread workgroup per (sequence, head), K and V in LDS ([L][65]), a wave per query row
-constexpr int MA_MAXL = 256;
+constexpr int MA_MAXL = MATTN_F32_MAXL;
 template <bool DROP>
 __global__ __launch_bounds__(256) void mattn_long_fwd_kernel(const float* __restrict__ qkv, const long* __restrict__ mask,
                                                              float* __restrict__ out, float* __restrict__ probs,
@@ -350,68 +351,17 @@ __global__ __launch_bounds__(256) void tanh_bwd_kernel(const float* __restrict__
     dz[i] = dy[i] * (1.0f - y[i] * y[i]);
 }
 
-// y[M,N] = x[M,K] w[N,K]^T (+ bias) (+ resid);  lda / ldc: row strides of x and y (0 = dense)
-inline int linear(const float* x, const float* w, float* y, int M, int N, int K, const float* bias, const float* resid, hipStream_t s,
-                  long lda = 0, int ldc = 0) {
-  return hmmc_gemm_f32(x, w, y, M, N, K, lda ? lda : K, 1, 1, K, ldc ? ldc : N, 1.0f, bias, resid, nullptr, nullptr,
-                       (bias ? EPI_BIAS : 0) | (resid ? EPI_RESID : 0), s);
-}
-// dx[M,K'] = dy[M,N'] w[N',K'] (+ resid);  ldy / ldx: row strides of dy and dx (0 = dense)
-inline int dgrad(const float* dy, const float* w, float* dx, int M, int Np, int Kp, const float* resid, hipStream_t s, long ldy = 0,
-                 int ldx = 0) {
-  return hmmc_gemm_f32(dy, w, dx, M, Kp, Np, ldy ? ldy : Np, 1, Kp, 1, ldx ? ldx : Kp, 1.0f, nullptr, resid, nullptr, nullptr,
-                       resid ? EPI_RESID : 0, s);
-}
-// dW[N',K'] = dy[T,N']^T x[T,K'];  ldy / ldx: row strides of dy and x (0 = dense)
-inline int wgrad(const float* dy, const float* x, float* dw, int T, int Np, int Kp, hipStream_t s, long ldy = 0, long ldx = 0) {
-  return hmmc_gemm_f32(dy, x, dw, Np, Kp, T, 1, ldy ? ldy : Np, ldx ? ldx : Kp, 1, Kp, 1.0f, nullptr, nullptr, nullptr, nullptr, 0, s);
-}
-
-// activation layout of hmmc_bert_fwd / hmmc_bert_bwd: the embedding's pre-LayerNorm rows and statistics, then one slab per
-// layer (keep_acts) or one slab that every layer reuses
-struct EmbActs { float *e, *mean, *rstd; size_t bytes; };
-struct LayerActs { float *x, *qkv, *probs, *praw, *att, *pre1, *x1, *h, *g, *pre2, *m1, *r1, *m2, *r2; size_t bytes; };
-EmbActs carve_emb(char* base, long T, int D) {
-  EmbActs a;
-  char* p = base;
-  a.e = (float*)p; p += al((size_t)T * D * 4);
-  a.mean = (float*)p; p += al((size_t)T * 4);
-  a.rstd = (float*)p; p += al((size_t)T * 4);
-  a.bytes = (size_t)(p - base);
-  return a;
-}
-LayerActs carve_layer(char* base, long T, int D, int I, int nseq, int L, int H, bool attn_drop) {
-  LayerActs a;
-  const size_t td = al((size_t)T * D * 4), ti = al((size_t)T * I * 4), pp = al((size_t)nseq * H * L * L * 4), tr = al((size_t)T * 4);
-  char* p = base;
-  a.x = (float*)p; p += td;
-  a.qkv = (float*)p; p += al((size_t)T * 3 * D * 4);
-  a.probs = (float*)p; p += pp;
-  a.praw = attn_drop ? (float*)p : nullptr; p += attn_drop ? pp : 0;
-  a.att = (float*)p; p += td;
-  a.pre1 = (float*)p; p += td;
-  a.x1 = (float*)p; p += td;
-  a.h = (float*)p; p += ti;
-  a.g = (float*)p; p += ti;
-  a.pre2 = (float*)p; p += td;
-  a.m1 = (float*)p; p += tr;
-  a.r1 = (float*)p; p += tr;
-  a.m2 = (float*)p; p += tr;
-  a.r2 = (float*)p; p += tr;
-  a.bytes = (size_t)(p - base);
-  return a;
-}
-
-constexpr int BERT_EMB_PARAMS = 5, BERT_LAYER_PARAMS = 16;
-inline bool bert_dims_ok(int nseq, int L, int heads, int D, int inter, int nlayers) {
-  return nseq > 0 && L > 0 && heads > 0 && nlayers > 0 && inter > 0 && D == heads * 64;
+// what the two attention entry points check alike
+int mattn_args_ok(const float* qkv, const long* mask, const float* probs, const float* probs_raw, int b, int L, int H, float p) {
+  if (!qkv || !mask || !probs || b <= 0 || L <= 0 || H <= 0 || !drop_p_ok(p) || (p > 0.f && !probs_raw)) return HMMC_ERR_ARG;
+  return L > MA_MAXL ? HMMC_ERR_UNSUPPORTED : HMMC_OK;
 }
 
 }  // namespace
 
 extern "C" int hmmc_dropout_fwd(const float* x, const float* resid, float* y, long n, float p, long seed, int site,
                                 hipStream_t stream) {
-  if (!x || !y || n <= 0 || !(p >= 0.f) || !(p < 1.f)) return HMMC_ERR_ARG;
+  if (!x || !y || n <= 0 || !drop_p_ok(p)) return HMMC_ERR_ARG;
   if ((n & 3) || (((uintptr_t)x | (uintptr_t)y | (uintptr_t)resid) & 15)) return HMMC_ERR_UNSUPPORTED;
   if (p == 0.f) {
     if (!resid && x == y) return HMMC_OK;
@@ -462,9 +412,8 @@ extern "C" int hmmc_bert_embed_bwd(const long* ids, const float* dy, const float
 
 extern "C" int hmmc_masked_attention_fwd(const float* qkv, const long* key_mask, float* out, float* probs, float* probs_raw, int b,
                                          int L, int H, float p, long seed, int site, hipStream_t stream) {
-  if (!qkv || !key_mask || !out || !probs || b <= 0 || L <= 0 || H <= 0 || !(p >= 0.f) || !(p < 1.f)) return HMMC_ERR_ARG;
-  if (p > 0.f && !probs_raw) return HMMC_ERR_ARG;
-  if (L > MA_MAXL) return HMMC_ERR_UNSUPPORTED;
+  if (!out) return HMMC_ERR_ARG;
+  CK(mattn_args_ok(qkv, key_mask, probs, probs_raw, b, L, H, p));
   const Drop dr = make_drop(p, seed, site);
   const dim3 grid(b * H);
   if (L > 64) {
@@ -482,9 +431,8 @@ extern "C" int hmmc_masked_attention_fwd(const float* qkv, const long* key_mask,
 extern "C" int hmmc_masked_attention_bwd(const float* qkv, const long* key_mask, const float* probs, const float* probs_raw,
                                          const float* dout, float* dqkv, int b, int L, int H, float p, long seed, int site,
                                          hipStream_t stream) {
-  if (!qkv || !key_mask || !probs || !dout || !dqkv || b <= 0 || L <= 0 || H <= 0 || !(p >= 0.f) || !(p < 1.f)) return HMMC_ERR_ARG;
-  if (p > 0.f && !probs_raw) return HMMC_ERR_ARG;
-  if (L > MA_MAXL) return HMMC_ERR_UNSUPPORTED;
+  if (!dout || !dqkv) return HMMC_ERR_ARG;
+  CK(mattn_args_ok(qkv, key_mask, probs, probs_raw, b, L, H, p));
   const Drop dr = make_drop(p, seed, site);
   const dim3 grid(b * H);
   if (L > 64) {
@@ -499,162 +447,11 @@ extern "C" int hmmc_masked_attention_bwd(const float* qkv, const long* key_mask,
   return hmmc_launch_status();
 }
 
-extern "C" int hmmc_bert_pooler_fwd(const float* x, const float* W, const float* bias, float* y, int b, long stride, int D,
-                                    hipStream_t stream) {
-  if (!x || !W || !bias || !y || b <= 0 || D <= 0 || stride < D) return HMMC_ERR_ARG;
-  CK(linear(x, W, y, b, D, D, bias, nullptr, stream, stride, 0));
-  hipLaunchKernelGGL(tanh_kernel, dim3(nblk((long)b * D)), dim3(256), 0, stream, y, (long)b * D);
+int bert_tanh_f32(float* y, long n, hipStream_t s) {
+  hipLaunchKernelGGL(tanh_kernel, dim3(nblk(n)), dim3(256), 0, s, y, n);
   return hmmc_launch_status();
 }
-
-extern "C" int hmmc_bert_pooler_bwd(const float* dy, const float* y, const float* x, const float* W, float* dz, float* dx, float* dW,
-                                    float* db, int b, long stride, int D, void* workspace, size_t ws_bytes, hipStream_t stream) {
-  if (!dy || !y || !x || !W || !dz || !dx || !dW || !db || b <= 0 || D <= 0 || stride < D) return HMMC_ERR_ARG;
-  if (stride > 0x7fffffffL) return HMMC_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(tanh_bwd_kernel, dim3(nblk((long)b * D)), dim3(256), 0, stream, dy, y, dz, (long)b * D);
-  CK(hmmc_launch_status());
-  CK(hmmc_colsum(dz, db, b, D, D, 1, 1, 0, workspace, ws_bytes, stream));
-  CK(wgrad(dz, x, dW, b, D, D, stream, 0, stride));
-  return dgrad(dz, W, dx, b, D, D, nullptr, stream, 0, (int)stride);
-}
-
-extern "C" size_t hmmc_bert_act_bytes(int nseq, int L, int heads, int D, int inter, int nlayers, int keep_acts, int attn_dropout) {
-  const long T = (long)nseq * L;
-  return carve_emb(nullptr, T, D).bytes +
-         carve_layer(nullptr, T, D, inter, nseq, L, heads, attn_dropout != 0).bytes * (size_t)(keep_acts ? nlayers : 1);
-}
-// transient gradients of the backward: six [T, D], two [T, inter], one [T, 3D]
-extern "C" size_t hmmc_bert_bwd_scratch_bytes(int nseq, int L, int D, int inter) {
-  const long T = (long)nseq * L;
-  return 6 * al((size_t)T * D * 4) + 2 * al((size_t)T * inter * 4) + al((size_t)T * 3 * D * 4);
-}
-extern "C" size_t hmmc_bert_workspace_bytes(int nseq, int L, int D, int inter) {
-  const int T = nseq * L;
-  size_t w = std::max(hmmc_layernorm_bwd_workspace(T, D), hmmc_colsum_workspace(T, inter));
-  w = std::max(w, hmmc_colsum_workspace(T, D));
-  return al(std::max(w, hmmc_bert_embed_bwd_workspace(T, L, D)));
-}
-
-extern "C" int hmmc_bert_fwd(const long* ids, const long* key_mask, float* y, const void* const* params, void* acts, int keep_acts,
-                             int nseq, int L, int heads, int D, int inter, int nlayers, long vocab, float eps, float p_hidden,
-                             float p_attn, long seed, int* err_flag, hipStream_t s) {
-  if (!ids || !key_mask || !y || !params || !acts || vocab <= 0 || !bert_dims_ok(nseq, L, heads, D, inter, nlayers)) return HMMC_ERR_ARG;
-  if (!(p_hidden >= 0.f) || !(p_hidden < 1.f) || !(p_attn >= 0.f) || !(p_attn < 1.f)) return HMMC_ERR_ARG;
-  if (L > MA_MAXL || D > 1024 || (inter & 3)) return HMMC_ERR_UNSUPPORTED;
-  const long T = (long)nseq * L;
-  if (T * std::max(3 * D, inter) > 0x7fffffffL) return HMMC_ERR_UNSUPPORTED;
-  const bool adrop = p_attn > 0.f;
-  const float* const* P = (const float* const*)params;
-  const EmbActs ea = carve_emb((char*)acts, T, D);
-  char* const slabs = (char*)acts + ea.bytes;
-  const size_t slab = carve_layer(nullptr, T, D, inter, nseq, L, heads, adrop).bytes;
-  LayerActs a = carve_layer(slabs, T, D, inter, nseq, L, heads, adrop);
-  // x0 = dropout(LN(word + pos + type 0)) into the first slab's input
-  CK(hmmc_bert_embed_fwd(ids, P[0], P[1], P[2], P[3], P[4], keep_acts ? ea.e : nullptr, a.x, ea.mean, ea.rstd, T, L, D, vocab, eps,
-                         err_flag, s));
-  CK(hmmc_dropout_fwd(a.x, nullptr, a.x, T * D, p_hidden, seed, 0, s));
-  for (int i = 0; i < nlayers; ++i) {
-    const float* const* W = P + BERT_EMB_PARAMS + (size_t)i * BERT_LAYER_PARAMS;
-    if (keep_acts) a = carve_layer(slabs + (size_t)i * slab, T, D, inter, nseq, L, heads, adrop);
-    // the layer's output: the next slab's input, y for the last layer; without kept activations the one slab's input slot,
-    // which is dead once attention.output.dense has read it as its residual
-    float* out = i + 1 == nlayers ? y : keep_acts ? carve_layer(slabs + (size_t)(i + 1) * slab, T, D, inter, nseq, L, heads, adrop).x : a.x;
-    for (int j = 0; j < 3; ++j)                                    // query | key | value into one [T, 3D] buffer
-      CK(linear(a.x, W[2 * j], a.qkv + (size_t)j * D, (int)T, D, D, W[2 * j + 1], nullptr, s, 0, 3 * D));
-    CK(hmmc_masked_attention_fwd(a.qkv, key_mask, a.att, a.probs, a.praw, nseq, L, heads, p_attn, seed, 1 + 3 * i, s));
-    if (p_hidden > 0.f) {
-      CK(linear(a.att, W[6], a.pre1, (int)T, D, D, W[7], nullptr, s));
-      CK(hmmc_dropout_fwd(a.pre1, a.x, a.pre1, T * D, p_hidden, seed, 2 + 3 * i, s));
-    } else {
-      CK(linear(a.att, W[6], a.pre1, (int)T, D, D, W[7], a.x, s));
-    }
-    CK(hmmc_layernorm_fwd(a.pre1, W[8], W[9], a.x1, a.m1, a.r1, nullptr, (int)T, D, D, eps, 1, s));
-    CK(linear(a.x1, W[10], a.h, (int)T, inter, D, W[11], nullptr, s));
-    CK(hmmc_gelu_erf_fwd(a.h, a.g, T * inter, s));
-    if (p_hidden > 0.f) {
-      CK(linear(a.g, W[12], a.pre2, (int)T, D, inter, W[13], nullptr, s));
-      CK(hmmc_dropout_fwd(a.pre2, a.x1, a.pre2, T * D, p_hidden, seed, 3 + 3 * i, s));
-    } else {
-      CK(linear(a.g, W[12], a.pre2, (int)T, D, inter, W[13], a.x1, s));
-    }
-    CK(hmmc_layernorm_fwd(a.pre2, W[14], W[15], out, a.m2, a.r2, nullptr, (int)T, D, D, eps, 1, s));
-  }
-  return HMMC_OK;
-}
-
-extern "C" int hmmc_bert_bwd(const float* dy, const long* ids, const long* key_mask, const void* const* params, void* const* grads,
-                             const void* acts, void* scratch, int nseq, int L, int heads, int D, int inter, int nlayers, long vocab,
-                             int max_pos, int type_vocab, float p_hidden, float p_attn, long seed, void* workspace, size_t ws_bytes,
-                             hipStream_t s) {
-  if (!dy || !ids || !key_mask || !params || !grads || !acts || !scratch || vocab <= 0 || !bert_dims_ok(nseq, L, heads, D, inter, nlayers))
-    return HMMC_ERR_ARG;
-  if (!(p_hidden >= 0.f) || !(p_hidden < 1.f) || !(p_attn >= 0.f) || !(p_attn < 1.f) || max_pos < L || type_vocab <= 0) return HMMC_ERR_ARG;
-  if (L > MA_MAXL || D > 1024 || (inter & 3)) return HMMC_ERR_UNSUPPORTED;
-  const long T = (long)nseq * L;
-  if (T * std::max(3 * D, inter) > 0x7fffffffL) return HMMC_ERR_UNSUPPORTED;
-  if (!workspace || ws_bytes < hmmc_bert_workspace_bytes(nseq, L, D, inter)) return HMMC_ERR_WORKSPACE;
-  const bool adrop = p_attn > 0.f, hdrop = p_hidden > 0.f;
-  const float* const* P = (const float* const*)params;
-  float* const* G = (float* const*)grads;
-  const EmbActs ea = carve_emb((char*)acts, T, D);
-  char* const slabs = (char*)acts + ea.bytes;
-  const size_t slab = carve_layer(nullptr, T, D, inter, nseq, L, heads, adrop).bytes;
-  char* sp = (char*)scratch;
-  float* td[6];
-  for (auto& t : td) { t = (float*)sp; sp += al((size_t)T * D * 4); }
-  float* const dA = td[0]; float* const dB = td[1]; float* const dC = td[2]; float* const dD = td[3];
-  float* const dg = (float*)sp; sp += al((size_t)T * inter * 4);
-  float* const dh = (float*)sp; sp += al((size_t)T * inter * 4);
-  float* const dqkv = (float*)sp;
-  const float* g_in = dy;
-  for (int i = nlayers - 1; i >= 0; --i) {
-    const float* const* W = P + BERT_EMB_PARAMS + (size_t)i * BERT_LAYER_PARAMS;
-    float* const* GW = G + BERT_EMB_PARAMS + (size_t)i * BERT_LAYER_PARAMS;
-    const LayerActs a = carve_layer(slabs + (size_t)i * slab, T, D, inter, nseq, L, heads, adrop);
-    float* const g_out = td[4 + (i & 1)];
-    // ---- out = LN(pre2), pre2 = dropout(g W_o^T + b_o) + x1: dA = d(pre2); without dropout its column sums are d(b_o)
-    CK(hmmc_layernorm_bwd(g_in, a.pre2, W[14], a.m2, a.r2, nullptr, dA, GW[14], GW[15], hdrop ? nullptr : GW[13], nullptr, (int)T, D, D, 1,
-                          workspace, ws_bytes, s));
-    const float* da2 = dA;
-    if (hdrop) {
-      CK(hmmc_dropout_bwd(dA, dB, T * D, p_hidden, seed, 3 + 3 * i, s));
-      CK(hmmc_colsum(dB, GW[13], (int)T, D, D, 1, 1, 0, workspace, ws_bytes, s));
-      da2 = dB;
-    }
-    CK(wgrad(da2, a.g, GW[12], (int)T, D, inter, s));
-    CK(dgrad(da2, W[12], dg, (int)T, D, inter, nullptr, s));
-    CK(hmmc_gelu_erf_bwd(a.h, dg, dh, T * inter, s));
-    CK(hmmc_colsum(dh, GW[11], (int)T, inter, inter, 1, 1, 0, workspace, ws_bytes, s));
-    CK(wgrad(dh, a.x1, GW[10], (int)T, inter, D, s));
-    CK(dgrad(dh, W[10], dC, (int)T, inter, D, dA, s));                  // d(x1): through intermediate.dense and the residual
-    // ---- x1 = LN(pre1), pre1 = dropout(att W_ao^T + b_ao) + x: dD = d(pre1)
-    CK(hmmc_layernorm_bwd(dC, a.pre1, W[8], a.m1, a.r1, nullptr, dD, GW[8], GW[9], hdrop ? nullptr : GW[7], nullptr, (int)T, D, D, 1,
-                          workspace, ws_bytes, s));
-    const float* da1 = dD;
-    if (hdrop) {
-      CK(hmmc_dropout_bwd(dD, dB, T * D, p_hidden, seed, 2 + 3 * i, s));
-      CK(hmmc_colsum(dB, GW[7], (int)T, D, D, 1, 1, 0, workspace, ws_bytes, s));
-      da1 = dB;
-    }
-    CK(wgrad(da1, a.att, GW[6], (int)T, D, D, s));
-    CK(dgrad(da1, W[6], dA, (int)T, D, D, nullptr, s));                 // d(att)
-    CK(hmmc_masked_attention_bwd(a.qkv, key_mask, a.probs, a.praw, dA, dqkv, nseq, L, heads, p_attn, seed, 1 + 3 * i, s));
-    for (int j = 0; j < 3; ++j) {
-      CK(hmmc_colsum(dqkv + (size_t)j * D, GW[2 * j + 1], (int)T, D, 3 * D, 1, 1, 0, workspace, ws_bytes, s));
-      CK(wgrad(dqkv + (size_t)j * D, a.x, GW[2 * j], (int)T, D, D, s, 3 * D, 0));
-    }
-    // d(x) = dq W_q + dk W_k + dv W_v + d(pre1), added in this order
-    CK(dgrad(dqkv, W[0], dC, (int)T, D, D, dD, s, 3 * D));
-    CK(dgrad(dqkv + D, W[2], dA, (int)T, D, D, dC, s, 3 * D));
-    CK(dgrad(dqkv + 2 * (size_t)D, W[4], g_out, (int)T, D, D, dA, s, 3 * D));
-    g_in = g_out;
-  }
-  // ---- x0 = dropout(LN(e)): the embedding tables and the embedding LayerNorm
-  const float* dx0 = g_in;
-  if (hdrop) {
-    CK(hmmc_dropout_bwd(g_in, dA, T * D, p_hidden, seed, 0, s));
-    dx0 = dA;
-  }
-  return hmmc_bert_embed_bwd(ids, dx0, ea.e, P[3], ea.mean, ea.rstd, dB, G[0], G[1], G[2], G[3], G[4], T, L, D, vocab, max_pos, type_vocab,
-                             workspace, ws_bytes, s);
+int bert_tanh_bwd_f32(const float* dy, const float* y, float* dz, long n, hipStream_t s) {
+  hipLaunchKernelGGL(tanh_bwd_kernel, dim3(nblk(n)), dim3(256), 0, s, dy, y, dz, n);
+  return hmmc_launch_status();
 }

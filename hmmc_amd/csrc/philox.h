@@ -1,4 +1,4 @@
-// Counter-based dropout shared by both regimes of the Chinese text branch (bert_f32.hip, bert_f16.hip): Philox4x32-10
+// Counter-based dropout shared by both regimes of the Chinese text branch (bert_f32.hip, bert_f16.hip, bert_tower.hip): Philox4x32-10
 // (Salmon et al., SC'11).  The keep decision of element `idx` of dropout site `site` is word (idx & 3) of
 // Philox(key = seed, counter = (idx >> 2, site)): a pure function of (seed, site, idx), so the backward regenerates it and
 // no mask is stored.
@@ -19,6 +19,7 @@ __device__ __forceinline__ void philox4x32_10(unsigned k0, unsigned k1, unsigned
   out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 struct Drop { unsigned k0, k1, site, thresh; float scale; };     // keep <=> word >= thresh;  scale = 1 / (1 - p)
+inline bool drop_p_ok(float p) { return p >= 0.f && p < 1.f; }   // the probabilities every entry point takes (a NaN is refused)
 inline Drop make_drop(float p, long seed, int site) {
   Drop d;
   d.k0 = (unsigned)((unsigned long)seed & 0xffffffffu); d.k1 = (unsigned)((unsigned long)seed >> 32);

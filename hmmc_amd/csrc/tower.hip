@@ -8,7 +8,7 @@
 //   acts    : one slab of hmmc_tower_act_bytes() per layer (saved for backward); layout below
 //   scratch : hmmc_tower_bwd_scratch_bytes() for the backward's transient gradients
 //   grads   : nlayers x 12 pointers, written (not accumulated)
-#include "common.h"
+#include "gemm_seq.h"
 #include "options.h"
 #include <algorithm>
 #include <cstring>
@@ -46,40 +46,6 @@ Acts carve(char* base, long T, int D, int nseq, int L, int H, int es, bool f32, 
   a.stat = (float*)p; p += al((size_t)nseq * H * L * (f32 ? L : 1) * 4);
   a.bytes = (size_t)(p - base);
   return a;
-}
-
-// y[M,N] = x[M,K] w[N,K]^T;  lda / ldc: row strides of x and of y (0 = dense)
-inline int linear(bool f32, const void* x, const void* w, void* y, int M, int N, int K, const void* bias, const void* resid,
-                  void* aux_out, int epi, hipStream_t s, int lda = 0, int ldc = 0) {
-  lda = lda ? lda : K;
-  ldc = ldc ? ldc : N;
-  epi |= (bias ? EPI_BIAS : 0) | (resid ? EPI_RESID : 0);
-  if (f32)
-    return hmmc_gemm_f32((const float*)x, (const float*)w, (float*)y, M, N, K, lda, 1, 1, K, ldc, 1.0f, (const float*)bias,
-                         (const float*)resid, (float*)aux_out, nullptr, epi, s);
-  return hmmc_gemm_f16(x, w, y, M, N, K, lda, K, ldc, 1, 1, bias, resid, aux_out, nullptr, epi, nullptr, 0, s);
-}
-// dx[M,K'] = dy[M,N'] w[N',K'];  ldy / ldx: row strides of dy and dx (0 = dense)
-// csum (fp16 tower only): fp32 partial column sums of dx, hmmc_gemm_f16_colsum_rows(M, K', N') rows of K' floats
-inline int dgrad(bool f32, const void* dy, const void* w, void* dx, int M, int Np, int Kp, const void* aux_in, int epi,
-                 hipStream_t s, int ldy = 0, int ldx = 0, float* csum = nullptr, size_t csum_bytes = 0) {
-  ldy = ldy ? ldy : Np;
-  ldx = ldx ? ldx : Kp;
-  if (f32)
-    return hmmc_gemm_f32((const float*)dy, (const float*)w, (float*)dx, M, Kp, Np, ldy, 1, Kp, 1, ldx, 1.0f, nullptr, nullptr,
-                         nullptr, (const float*)aux_in, epi, s);
-  return hmmc_gemm_f16(dy, w, dx, M, Kp, Np, ldy, Kp, ldx, 1, 0, nullptr, nullptr, nullptr, aux_in, epi | (csum ? EPI_COLSUM : 0),
-                       csum, csum_bytes, s);
-}
-// dW[N',K'] = dy[T,N']^T x[T,K'];  ldy / ldx: row strides of dy and x (0 = dense)
-inline int wgrad(bool f32, const void* dy, const void* x, void* dw, int T, int Np, int Kp, void* ws, size_t wsb, hipStream_t s,
-                 int ldy = 0, int ldx = 0) {
-  if (f32)
-    return hmmc_gemm_f32((const float*)dy, (const float*)x, (float*)dw, Np, Kp, T, 1, Np, Kp, 1, Kp, 1.0f, nullptr, nullptr,
-                         nullptr, nullptr, 0, s);
-  size_t need = hmmc_gemm_f16_workspace(Np, Kp, T);
-  return hmmc_gemm_f16(dy, x, dw, Np, Kp, T, ldy ? ldy : Np, ldx ? ldx : Kp, Kp, 0, 0, nullptr, nullptr, nullptr, nullptr, 0,
-                       need <= wsb ? ws : nullptr, need <= wsb ? wsb : 0, s);
 }
 
 // The attention half of a LAST block whose caller reads the class token alone (lead_only), sequences of at most 256 tokens: only
@@ -625,7 +591,7 @@ static int tower_bwd_impl(const void* dy, void* dx, const void* x0, const void* 
     if (!group_layer) CK(side_wgrad(0, g_in, a.g, G[10], D, 4 * D, R, ldr, 0));
     CK(before_overwrite(1));
     if (f32) {
-      CK(dgrad(f32, g_in, P[10], dh, (int)T, D, 4 * D, a.h, EPI_DGELU, s));
+      CK(dgrad(f32, g_in, P[10], dh, (int)T, D, 4 * D, nullptr, a.h, EPI_DGELU, s));
       CK(hmmc_colsum(dh, G[9], (int)T, 4 * D, 4 * D, dt, dt, 0, workspace, gen, s));
     } else {
       const size_t fc_bytes = slot.attn - slot.fc;
@@ -633,11 +599,11 @@ static int tower_bwd_impl(const void* dy, void* dx, const void* x0, const void* 
         CK(hmmc_gemm_f16_fold(g_in, P[10], dh, (int)T, 4 * D, D, D, 4 * D, 4 * D, 0, nullptr, nullptr, nullptr, a.h,
                               EPI_MULAUX | EPI_COLSUM | EPI_ROWSCALE, a.m2, nullptr, nullptr, p_fc, fc_bytes, s));
       else
-        CK(dgrad(f32, g_in, P[10], dh, R, D, 4 * D, a.h, EPI_MULAUX, s, ldr, 0, p_fc, fc_bytes));
+        CK(dgrad(f32, g_in, P[10], dh, R, D, 4 * D, nullptr, a.h, EPI_MULAUX, s, ldr, 0, p_fc, fc_bytes));
       defer(p_fc, (int)hmmc_gemm_f16_colsum_rows(R, 4 * D, D), 4 * D, 4 * D, G[9], dt);
     }
     if (!group_layer) CK(side_wgrad(1, dh, a.ln2, G[8], 4 * D, D, R));
-    CK(dgrad(f32, dh, f ? f->w2 : P[8], dln, R, 4 * D, D, nullptr, 0, s));              // folded: du~2
+    CK(dgrad(f32, dh, f ? f->w2 : P[8], dln, R, 4 * D, D, nullptr, nullptr, 0, s));              // folded: du~2
     CK(before_overwrite(2));
     if (f) CK(ln_bwd_folded(dln, a.x1, a.m2, g_in, dx1, G[5], (int)T, D, p_ln2));     // G[5]: out_proj bias = colsum(dx1)
     else CK(ln_bwd(dln, a.x1, (const float*)P[6], a.m2, a.r2, g_in, dx1, (float*)G[6], (float*)G[7], G[5], R, ldr, p_ln2));
@@ -645,7 +611,7 @@ static int tower_bwd_impl(const void* dy, void* dx, const void* x0, const void* 
     // the attention of a lead_attention() block reads datt on the leading rows alone
     const bool lead_attn = lead_attention(lead, f32, L);
     if (lead && !lead_attn) HIPCK(hipMemsetAsync(dln, 0, (size_t)T * D * es, s));
-    CK(dgrad(f32, dx1, P[4], dln, R, D, D, nullptr, 0, s, ldr, ldr));                    // datt
+    CK(dgrad(f32, dx1, P[4], dln, R, D, D, nullptr, nullptr, 0, s, ldr, ldr));                    // datt
     // ---- attention, x1 = x + out_proj(attn(in_proj(ln1))): dqkv, the layer's remaining weight gradients and dln = d(ln1)
     CK(before_overwrite(3));
     if (f32) {
@@ -667,8 +633,8 @@ static int tower_bwd_impl(const void* dy, void* dx, const void* x0, const void* 
       const half_t* const w_in = (const half_t*)P[2];
       CK(side_wgrad(3, dqkv_h + D, a.ln1, gw + (size_t)D * D, 2 * D, D, (int)T, 3 * D, 0));
       CK(side_wgrad(3, dqkv_h, a.ln1, gw, D, D, nseq, L * 3 * D, ldl));
-      CK(dgrad(f32, dqkv_h + D, w_in + (size_t)D * D, dln, (int)T, 2 * D, D, nullptr, 0, s, 3 * D, 0));
-      CK(dgrad(f32, dqkv_h, w_in, dln, nseq, 3 * D, D, nullptr, 0, s, L * 3 * D, ldl));
+      CK(dgrad(f32, dqkv_h + D, w_in + (size_t)D * D, dln, (int)T, 2 * D, D, nullptr, nullptr, 0, s, 3 * D, 0));
+      CK(dgrad(f32, dqkv_h, w_in, dln, nseq, 3 * D, D, nullptr, nullptr, 0, s, L * 3 * D, ldl));
     } else {
       if (group_layer) {
         // all four weight gradients of the layer in one launch, now that the last operand (dqkv) exists.  A folded layer's
@@ -688,7 +654,7 @@ static int tower_bwd_impl(const void* dy, void* dx, const void* x0, const void* 
       } else {
         CK(side_wgrad(3, dqkv, a.ln1, G[2], 3 * D, D));
       }
-      CK(dgrad(f32, dqkv, f ? f->w1 : P[2], dln, (int)T, 3 * D, D, nullptr, 0, s));       // folded: du~1
+      CK(dgrad(f32, dqkv, f ? f->w1 : P[2], dln, (int)T, 3 * D, D, nullptr, nullptr, 0, s));       // folded: du~1
     }
     // ---- ln_1.  Its dx goes to g_out, the buffer the layer above read as g_in (weight gradient 0 or its grouped launch); the
     // column sum of that dx is the c_proj bias gradient of the layer below

@@ -430,7 +430,8 @@ int hmmc_bert_pooler_fwd(const float* x, const float* W, const float* bias, floa
                          hmmc_stream_t stream);
 int hmmc_bert_pooler_bwd(const float* dy, const float* y, const float* x, const float* W, float* dz, float* dx, float* dW,
                          float* db, int b, long stride, int D, void* workspace, size_t ws_bytes, hmmc_stream_t stream);
-/* Tower runtime: BertEmbeddings and all BertLayers in one call each way; y [nseq*L, D] = last_hidden_state.
+/* Tower runtime (csrc/bert_tower.hip, which sequences both regimes): BertEmbeddings and all BertLayers in one call each way;
+ * y [nseq*L, D] = last_hidden_state.
  * params / grads: 5 + 16 * nlayers fp32 pointers in the order embeddings.{word_embeddings, position_embeddings,
  * token_type_embeddings}.weight, embeddings.LayerNorm.{weight, bias}, then per layer attention.self.{query, key, value}.{weight,
  * bias}, attention.output.dense.{weight, bias}, attention.output.LayerNorm.{weight, bias}, intermediate.dense.{weight, bias},
@@ -457,7 +458,7 @@ int hmmc_bert_bwd(const float* dy, const long* ids, const long* key_mask, const 
  * nn.Linear weight and bias is fp16, the three embedding tables and every LayerNorm parameter stay fp32.  Embedding, its
  * LayerNorm and dropout site 0 run on the fp32 entry points above, followed by one hmmc_cast; from there the residual stream and
  * every saved activation are fp16, every GEMM is hmmc_gemm_f16, LayerNorm is dtype 0 with the config's eps.  The rounding points
- * are listed at the top of csrc/bert_f16.hip.
+ * are listed at the top of csrc/bert_f16.hip, which holds the regime's kernels; csrc/bert_tower.hip sequences them.
  *
  * Key-masked fp16 MFMA attention, head dim 64, 1 <= L <= 64 (L > 64: HMMC_ERR_UNSUPPORTED), the contract of
  * hmmc_masked_attention_fwd: key_mask int64 [b, L], nonzero = valid key, any pattern; masked keys get probability exactly 0 and

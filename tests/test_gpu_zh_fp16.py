@@ -164,9 +164,9 @@ PRE = "text_encoder."
 LENS = [16, 1, 9, 5]
 
 
-def _tower_params(sd):
-    """GPU leaves in the converted layout + the argument list of functional.bert_text"""
-    half = {k for k in sd if not ("embeddings." in k or "LayerNorm." in k)}
+def _tower_params(sd, fp16=True):
+    """GPU leaves in the converted layout (fp16 = False: all fp32) + the argument list of functional.bert_text"""
+    half = {k for k in sd if fp16 and not ("embeddings." in k or "LayerNorm." in k)}
     g = {k: (v.half() if k in half else v.clone()).to(DEV).requires_grad_() for k, v in sd.items()}
     e = PRE + "chinese_encoder.embeddings."
     emb = [g[e + n] for n in ("word_embeddings.weight", "position_embeddings.weight", "token_type_embeddings.weight",
@@ -221,6 +221,39 @@ def test_tower_fwd_bwd_vs_fp64(want, p):
             continue
         assert g[k].grad.dtype == g[k].dtype, k
         held(f"tower {want} p={p} d {k[len(PRE):]}", g[k].grad, w64[k].grad, g16[k])
+
+
+@pytest.mark.parametrize("L", [7, 64])
+@pytest.mark.parametrize("regime", ["fp32", "fp16"])
+def test_reused_slab_equals_kept_slabs_and_the_backward_repeats(regime, L):
+    """The slab aliasing of the one tower runtime (csrc/bert_tower.hip), both regimes, with dropout at every site: a pass that
+    keeps no activations (every layer in ONE slab, its output in the slab's own input slot) returns the bits of a pass that keeps
+    one slab per layer, and a second forward + backward through freshly kept activations reproduces every gradient bit for bit.
+    (test_tower_fwd_bwd_vs_fp64 asserts the first half for fp16 at L = 16 on its way.)"""
+    from hmmc_amd import functional as Fn
+    bd = synth.ZH_TINY
+    b, p, seed = 3, 0.1, 97531
+    sd = synth.bert_state(bd, seed=5)
+    ids, mask = [t.to(DEV) for t in synth.zh_token_ids("zh_slab", b, L, bd.vocab_size, lens=[L, 1, max(2, 2 * L // 3)])]
+    cfg = (bd.num_attention_heads, bd.intermediate_size, 1e-12, p, p, seed)
+    for want in ("feat", "hidden"):
+        dout = rnd(f"slab.dout.{want}", (b, L, 512) if want == "hidden" else (b, 512)).to(DEV)
+
+        def kept():
+            g, args = _tower_params(sd, fp16=regime == "fp16")
+            y = Fn.bert_text(ids, mask, cfg, want, *args)
+            y.backward(dout)
+            return y.detach(), {k: v.grad for k, v in g.items() if v.grad is not None}, args
+
+        y1, g1, args = kept()
+        y2, g2, _ = kept()
+        with torch.no_grad():
+            y0 = Fn.bert_text(ids, mask, cfg, want, *args)
+        assert bool(torch.isfinite(y1).all()) and len(g1) >= len(sd) - 2
+        assert torch.equal(y0, y1), f"{regime} {want} L={L}: the one reused slab and the kept slabs differ"
+        assert torch.equal(y1, y2) and g1.keys() == g2.keys()
+        for k in g1:
+            assert torch.equal(g1[k], g2[k]), f"{regime} {want} L={L}: d {k} differs between two backwards"
 
 
 def test_merged_encode_many_pass_vs_fp64_sum_of_separate_passes():

@@ -1,5 +1,5 @@
-"""Plain fp64 statements of the fp16 hot path - the GEMM epilogues (gemm_f16.hip), the fused attention (attention_f16.hip,
-attention_long_f16.hip) and LayerNorm (norm_elem.hip) - and the per-element rounding bounds tests/test_gpu_hotpath.py holds the
+"""Plain fp64 statements of the fp16 hot path - the GEMM epilogues and the fp32 split-K slab paths of the weight gradients
+(gemm_f16.hip), the fused attention (attention_f16.hip, attention_long_f16.hip) and LayerNorm (norm_elem.hip) - and the per-element rounding bounds tests/test_gpu_hotpath.py holds the
 HIP kernels to.  tests/test_hotpath_reference.py pins each statement (torch.nn.functional in fp64, the oracle, autograd), shows
 with a torch emulation of each kernel's arithmetic that the bounds are not too tight, and with test_slip_* that they are not too
 loose.  U, SLACK and exp_rel are those of heads_ref.
@@ -20,6 +20,8 @@ propagated to first order to the output.  The rounding points, as read off the k
                         t = fp16(1.702 h), s = fp16(sigmoid(t)), out = fp16(h s);  aux = h, or fp16(QuickGELU'(h)) from the
                         fp32 sigmoid;  fp16(acc QuickGELU'(aux));  fp16(acc aux)
   COLSUM                fp32 sums of the fp16 values written to C: one partial row per 128 (256x256 tile) or 64 rows
+  split-K slabs         fp32 partial sums per K split (no rounding to fp16), added in split order by the reduce; ONE rounding to
+                        fp16 at the end, none for the grouped launch's fp32 output dW32 (wgrad_bound)
   LayerNorm             fp32 statistics; the stored y / dx (fp16 towers), the fp16 column sums of dx
 Bounds are functions of the fp64 reference and the inputs only, never of a kernel's output.  Plain functions, no fixtures."""
 from __future__ import annotations
@@ -413,6 +415,188 @@ def colsum_blocks(c, block):
 def colsum_bound(c, block):
     """bound of every COLSUM partial row: block / 16 strips added in a lane, then a 16-lane tree of 4"""
     return (block // 16 + 4) * U * colsum_blocks(c.abs(), block)
+
+
+# ============================================================================= weight gradients: fp32 split-K slabs + reduce
+
+BKT = 64                      # rows of a K-tile (gemm_f16.hip)
+
+
+def wgrad(dy, x):
+    """dW[n][k] = sum_t dy[t][n] x[t][k]: F.linear's weight gradient (modules/module_clip.py:231-257), fp64"""
+    return dy.t() @ x
+
+
+def gemm_kk(a, b):
+    """a [M, K] b [N, K]^T: the forward layout without an epilogue"""
+    return a @ b.t()
+
+
+def gemm_km(a, b):
+    """a [M, K] b [K, N]: the data-gradient layout without an epilogue"""
+    return a @ b
+
+
+def as_wgrad(layout, a, b):
+    """the operands of a kk / km / mm product as (dy [T, M], x [T, N]) with the reduction over the rows: every layout is then
+    wgrad(dy, x), and the split, the slips and the emulation below are written once"""
+    return {"mm": (a, b), "kk": (a.t(), b.t()), "km": (a.t(), b)}[layout]
+
+
+def split_plan(T, s):
+    """the host's split arithmetic (gemm_f16_one, group_plan) from the split count s the ABI reports for T reduction rows
+    -> (nkt, ktps, splitk): K-tiles, K-tiles per split = ceil(nkt / s), splits that own at least one K-tile = ceil(nkt / ktps).
+    The last split holds nkt - (splitk - 1) ktps K-tiles.  (Applying it to its own splitk gives the same ktps again.)"""
+    nkt = (T + BKT - 1) // BKT
+    ktps = (nkt + max(s, 1) - 1) // max(s, 1)
+    return nkt, ktps, (nkt + ktps - 1) // ktps
+
+
+def wgrad_bound(ref, abs_prod, T, ktps=None, slabs=1, half=True):
+    """Bound of a product that leaves through the fp32 slabs.  The operands are exact fp16 and every product is exact in fp32; the
+    accumulation error is c U sum_t |dy[t][n] x[t][k]| (abs_prod = |dy|^T |x|) with c the dependent fp32 additions behind an
+    element: 64 per K-tile of a split (at most: the MFMA adds 32 terms per instruction), plus one per slab summed by the ordered
+    reduce; c = T when the split is not known (ktps None: a T-term dot product).  half: the one rounding of the sum to fp16,
+    r16(ref); the fp32 output dW32 is the reduce's sum itself and adds nothing.
+    Two data regimes go with it, because on zero-mean data sum|ab| >> |sum ab| and the bound, dominated by r16(ref), cannot see a
+    slab that was rounded to fp16: "signed" (Gaussian: cancellation exposes sign and index slips) and "same" (dy, x in [0.25, 1]:
+    sum|ab| = |sum ab|, the fp32 bound is c U relative, far below U16).  The "exact" regime (small non-negative integers, every
+    slab past 2048 and every sum below 2^24, wgrad_inputs) is the strict form: the fp32 path is exact there and the tests compare with torch.equal."""
+    c = T if ktps is None else BKT * ktps + slabs
+    b = c * U * abs_prod
+    return b + r16(ref) if half else b
+
+
+WGRAD_REGIMES = ("signed", "same")
+
+
+def exact_top(T):
+    """largest integer operand of the exact regime: the mean result (m / 2)^2 T stays at 40000 or below (the largest a few
+    standard deviations higher, below 65504), which from T = 1000 on puts a 256-row split's partial, (m / 2)^2 256, past 2048;
+    m^2 T < 2^24 keeps every fp32 sum exact whatever the data.  Integers 0 .. 3 would do for the reduce alone - the RUNNING sum
+    passes 2048 - but a slab of 256 .. 448 rows would stay below 2048 and an fp16 slab would go unseen."""
+    m = int(2.0 * (40000.0 / T) ** 0.5)
+    assert m >= 3 and m * m * T < 2 ** 24, T
+    return m
+
+
+def wgrad_inputs(regime, T, dims, seed=0, device="cpu"):
+    """fp16 ([dy_j [T, Np_j]], [x_j [T, Kp_j]]) for dims = [(Np_j, Kp_j)]; every problem has data of its own.
+      signed  dy ~ N(0, 1), x ~ N(0, 1 / T): results of unit size
+      same    dy, x in [0.25, 1] times a scale that keeps every T-term sum below 32768 (fp16 holds the result)
+      exact   integers 0 .. m, m = exact_top(T): every partial sum is an integer below m^2 T < 2^24, so the fp32 path is exact; a
+              split's partial alone passes 2048 (from 4 K-tiles per split on, what both host policies keep), where fp16 holds
+              even numbers only, and the results stay near 40000, inside fp16's range"""
+    g = torch.Generator(device=device).manual_seed(100 * seed + T + sum(n + 3 * k for n, k in dims))
+    dys, xs = [], []
+    for n, k in dims:
+        if regime == "signed":
+            dy, x = torch.randn(T, n, generator=g, device=device), torch.randn(T, k, generator=g, device=device) / T ** 0.5
+        elif regime == "same":
+            sc = min(1.0, (32768.0 / T) ** 0.5)
+            dy = (0.25 + 0.75 * torch.rand(T, n, generator=g, device=device)) * sc
+            x = (0.25 + 0.75 * torch.rand(T, k, generator=g, device=device)) * sc
+        else:
+            assert regime == "exact", regime
+            m = exact_top(T)
+            dy = torch.randint(0, m + 1, (T, n), generator=g, device=device).float()
+            x = torch.randint(0, m + 1, (T, k), generator=g, device=device).float()
+        dys.append(dy.half())
+        xs.append(x.half())
+    return dys, xs
+
+
+def wgrad_partials(dy, x, ktps):
+    """[splitk, N, K]: split s sums the rows 64 ktps s .. 64 ktps (s + 1) - 1 (the last one what is left of T)"""
+    rows = BKT * ktps
+    return torch.stack([dy[r:r + rows].t() @ x[r:r + rows] for r in range(0, dy.shape[0], rows)])
+
+
+WGRAD_SLIPS = ("slab_f16", "reduce_f16", "split_dropped", "split_twice", "tail_rows", "acc_not_cleared")
+WGRAD_GROUP_SLIPS = WGRAD_SLIPS + ("problem_swapped",)
+
+
+def wgrad_slipped(dy, x, ktps, slip, tile=128):
+    """wgrad(dy, x) in fp64 through the slabs with one plausible mistake (dy, x fp64; returned before the final fp16 rounding):
+      slab_f16         each split's partial rounded to fp16 before the reduce
+      reduce_f16       the running sum rounded to fp16 between splits
+      split_dropped    the last, shorter split is missing
+      split_twice      one split counted twice, as with a stale slab
+      tail_rows        the rows T .. 64 nkt - 1 behind the operands are not treated as zero (here they repeat rows 0 ..)
+      acc_not_cleared  an item starts from the previous item's accumulator: the output tile to the right of (or, in a single column
+                       of tiles, below) a tile also holds that tile's partial of the first split"""
+    parts = wgrad_partials(dy, x, ktps)
+    if slip == "slab_f16":
+        return h16(parts).sum(0)
+    if slip == "reduce_f16":
+        run = parts[0]
+        for p in parts[1:]:
+            run = h16(run + p)
+        return run
+    if slip == "split_dropped":
+        return parts[:-1].sum(0)
+    if slip == "split_twice":
+        return parts.sum(0) + parts[0]
+    if slip == "tail_rows":
+        n = -dy.shape[0] % BKT
+        return parts.sum(0) + dy[:n].t() @ x[:n]
+    assert slip == "acc_not_cleared", slip
+    out = parts.sum(0)
+    if out.shape[1] > tile:
+        out[:, tile:] += parts[0][:, :-tile]
+    elif out.shape[0] > tile:
+        out[tile:] += parts[0][:-tile]
+    else:
+        out += parts[0]
+    return out
+
+
+def wgrad_group_swapped(dys, xs, ktps):
+    """problem_swapped: the grouped reduce of problem j reads from problem j - 1's slab offset (problem 0 is right).  The slabs
+    lie as [problem][split][Np_j Kp_j]; the reduce adds element e of its problem at offset + split Np_j Kp_j + e."""
+    parts = [wgrad_partials(dy, x, ktps) for dy, x in zip(dys, xs)]
+    flat = torch.cat([p.reshape(-1) for p in parts])
+    offs, o = [], 0
+    for p in parts:
+        offs.append(o)
+        o += p.numel()
+    outs = []
+    for j, p in enumerate(parts):
+        S, n, k = p.shape
+        off = offs[max(j - 1, 0)]
+        outs.append(flat[off:off + S * n * k].reshape(S, n, k).sum(0))
+    return outs
+
+
+def emulate_splitk(dy, x, ktps, half=True):
+    """gemm_f16.hip's slab path in torch: per split an fp32 accumulator that takes the K-tiles in order, 32 rows per MFMA
+    instruction; the reduce adds the slabs in split order in fp32; one rounding to fp16 (half) or none (dW32)"""
+    df, xf = dy.float(), x.float()
+    T, rows, total = dy.shape[0], BKT * ktps, None
+    for r0 in range(0, T, rows):
+        acc = torch.zeros(dy.shape[1], x.shape[1], dtype=torch.float32, device=dy.device)
+        for r in range(r0, min(T, r0 + rows), 32):
+            acc += df[r:r + 32].t() @ xf[r:r + 32]
+        total = acc if total is None else total + acc
+    return total.half() if half else total
+
+
+# the shapes tests/test_gpu_hotpath.py runs and tests/test_hotpath_reference.py emulates.  Single launches (M, N, K) in the
+# weight-gradient layout; the path each reaches on 256 CUs is named in test_gpu_hotpath.py
+WGRAD_MM_CASES = [(136, 264, 8), (136, 264, 100), (136, 264, 1000), (136, 264, 1001), (136, 264, 2120), (1024, 1024, 6152)]
+WGRAD_KX_CASES = [("kk", 128, 128, 2048), ("km", 128, 128, 2048)]
+WGRAD_LAYER = [(256, 1024), (1024, 256), (256, 256), (768, 256)]         # c_proj, c_fc, out_proj, in_proj at D = 256
+# grouped launches: name -> (dims, T, which problems leave as fp32 dW32)
+WGRAD_GROUP_CASES = {
+    "min_f16": ([(256, 256)], 512, ()),
+    "two_f32": ([(256, 256), (512, 256)], 520, (0, 1)),
+    "three_mix": (WGRAD_LAYER[:3], 1000, (1,)),
+    "layer_f16": (WGRAD_LAYER, 512, ()),
+    "layer_f32": (WGRAD_LAYER, 1001, (0, 1, 2, 3)),
+    "layer_mix": (WGRAD_LAYER, 2120, (1, 3)),
+    "wide_mix": ([(1024, 1280)] * 4, 512, (1, 3)),
+    "wide_1k_mix": ([(1024, 1280)] * 4, 1024, (1, 3)),
+}
 
 
 # ============================================================================= LayerNorm

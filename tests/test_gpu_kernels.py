@@ -84,10 +84,11 @@ def test_gemm_big_tile_exact_integers(layout, M, N, K):
 def test_gemm_grouped_weight_gradients_exact_integers(T, D):
     """The four weight gradients of a layer in one grouped launch (hmmc_gemm_f16_wgrad_group): bit-exact on integer data
     against fp32 torch for every problem, and the same results as one hmmc_gemm_f16 call per gradient.  Token counts: multiples
-    of the 64-token K tile (2048 ... 40000), counts that are not (2056, 5000, 12344: the K tail of the grouped kernel; T % 8 == 0
-    is the operand alignment), and 2120 tokens = 34 K-tiles, whose last split holds fewer K-tiles than the others.  Round 5: the
-    launch takes 512 tokens and more (the text tower at 32 captions per GPU has 1 024; 1 440 = 32 titles of 45): 512 / 1024 / 1000 /
-    520 / 1440 tokens - 8 to 23 K-tiles, one or two K-tiles per split at the short end."""
+    of the 64-token K tile (2048 ... 40000), counts that are not (2056, 5000, 12344: the K tail of the grouped kernel.  The token
+    count itself needs no alignment - rows lie Np / Kp halves apart and the rows from T on are past the buffer descriptor's byte
+    count; tests/test_gpu_hotpath.py runs 1001 tokens), and 2120 tokens = 34 K-tiles, whose last split holds fewer K-tiles than
+    the others.  Round 5: the launch takes 512 tokens and more (the text tower at 32 captions per GPU has 1 024; 1 440 = 32 titles
+    of 45): 512 / 1024 / 1000 / 520 / 1440 tokens - 8 to 23 K-tiles, at least four K-tiles per split (group_plan)."""
     g = torch.Generator().manual_seed(T + D)
     dims = [(D, 4 * D), (4 * D, D), (D, D), (3 * D, D)]                      # c_proj, c_fc, out_proj, in_proj
     dys = [torch.randint(-2, 3, (T, n), generator=g).half().to(DEV) for n, _ in dims]

@@ -1,6 +1,7 @@
 """CPU checks of tests/hotpath_ref.py, the fp64 statements and rounding bounds behind tests/test_gpu_hotpath.py:
   * every statement is pinned: attention and LayerNorm to torch.nn.functional in fp64 and to the oracle, the written-out attention
-    backward to autograd, QuickGELU and its derivative to the oracle and autograd, the GEMM epilogue formulas to F.linear + autograd;
+    backward to autograd, QuickGELU and its derivative to the oracle and autograd, the GEMM epilogue formulas to F.linear + autograd, the weight
+    gradient to torch.matmul and F.linear's autograd;
   * the bounds are not too tight: a torch emulation of each kernel's arithmetic (fp32, .half() at the kernel's rounding points) lies
     inside SLACK x bound in every input regime the GPU tests use (the worst err / (SLACK bound) per output is in the message and,
     with -s, on stdout);
@@ -322,3 +323,132 @@ def test_slip_layernorm(dtype, D, eps, regime):
     assert any(HR.detects(r, s, b[n]) for r, s, n in zip(ref, unb, names)), "unbiased variance"
     nb = HR.layernorm(x, gamma, beta, eps, mean_shift=1)
     assert HR.detects(ref[0], nb[0], b["y"]) and HR.detects(ref[1], nb[1], b["mean"]), "mean of the neighbouring row"
+
+
+# ============================================================================= weight gradients: split-K slabs + reduce
+
+def split_counts(T):
+    """split counts to emulate a shape with: none, two, and the most either host policy grants (four K-tiles per split)"""
+    nkt = (T + HR.BKT - 1) // HR.BKT
+    return sorted({1, min(2, nkt), max(1, nkt // 4)})
+
+
+def wgrad_case(regime, T, dims, seed=0):
+    dys, xs = HR.wgrad_inputs(regime, T, dims, seed)
+    return dys, xs, [d.double() for d in dys], [x.double() for x in xs]
+
+
+def test_wgrad_is_matmul_and_autograd():
+    T, N, K = 70, 24, 40
+    dy, x, w = randn(T, N, seed=1), randn(T, K, seed=2), randn(N, K, seed=3).requires_grad_()
+    assert_close(HR.wgrad(dy, x), torch.matmul(dy.transpose(0, 1), x), 0.0, "wgrad vs torch.matmul")
+    F.linear(x, w).backward(dy)
+    assert_close(HR.wgrad(dy, x), w.grad, 1e-13, "wgrad vs autograd of F.linear")
+    a, b, bt = randn(N, T, seed=4), randn(K, T, seed=5), randn(T, K, seed=6)
+    assert_close(HR.gemm_kk(a, b), torch.matmul(a, b.transpose(0, 1)), 0.0, "kk")
+    assert_close(HR.gemm_km(a, bt), torch.matmul(a, bt), 0.0, "km")
+    assert_close(HR.wgrad(*HR.as_wgrad("kk", a, b)), HR.gemm_kk(a, b), 1e-13, "kk as a weight gradient")
+    assert_close(HR.wgrad(*HR.as_wgrad("km", a, bt)), HR.gemm_km(a, bt), 1e-13, "km as a weight gradient")
+    # the slabs add up, whatever the split; a split count is turned into (nkt, ktps, splitk) as the host does
+    for ktps in (1, 2):
+        assert_close(HR.wgrad_partials(dy, x, ktps).sum(0), HR.wgrad(dy, x), 1e-12, "partials")
+    assert HR.split_plan(2120, 8) == (34, 5, 7) and HR.split_plan(2120, 7) == (34, 5, 7)       # a shorter last split: 34 - 30 = 4
+    assert HR.split_plan(1000, 4) == (16, 4, 4) and HR.split_plan(8, 0) == (1, 1, 1) and HR.split_plan(100, 1) == (2, 2, 1)
+    assert HR.split_plan(520, 2) == (9, 5, 2) and HR.split_plan(6152, 16) == (97, 7, 14)
+
+
+WGRAD_SHAPES = [(K, [(M, N)]) for M, N, K in HR.WGRAD_MM_CASES] + [(K, [(M, N)]) for _, M, N, K in HR.WGRAD_KX_CASES] + \
+    [(T, dims) for dims, T, _ in HR.WGRAD_GROUP_CASES.values()]
+
+
+@pytest.mark.parametrize("regime", HR.WGRAD_REGIMES)
+@pytest.mark.parametrize("T,dims", WGRAD_SHAPES, ids=[f"T{T}-{len(d)}x{d[0][0]}x{d[0][1]}" for T, d in WGRAD_SHAPES])
+def test_emulation_inside_bounds_wgrad(T, dims, regime):
+    """the slab path's arithmetic (fp32 per split in K-tile order, the ordered reduce, one fp16 rounding or none) lies inside the
+    bound of its split, and the unsplit emulation inside the c = T bound, at every shape the GPU tests run"""
+    ratios = {}
+    seen = set()
+    for (n, k), dy, x, d64, x64 in zip(dims, *wgrad_case(regime, T, dims)):
+        if (n, k) in seen:
+            continue
+        seen.add((n, k))
+        ref, ab = HR.wgrad(d64, x64), HR.wgrad(d64.abs(), x64.abs())
+        assert float(ref.abs().max()) < 65504
+        for s in split_counts(T):
+            nkt, ktps, splitk = HR.split_plan(T, s)
+            for half in (True, False):
+                emu = HR.emulate_splitk(dy, x, ktps, half)
+                worst(ratios, emu, ref, HR.wgrad_bound(ref, ab, T, ktps, splitk, half), "f16" if half else "f32")
+                if splitk == 1:
+                    worst(ratios, emu, ref, HR.wgrad_bound(ref, ab, T, half=half), ("f16" if half else "f32") + ".cT")
+    print(f"hotpath-emulation wgrad {regime} T {T}: " + ", ".join(f"{k} {v:.3f}" for k, v in ratios.items()))
+    assert max(ratios.values()) <= 1.0, f"weight gradient, {regime}: worst err / (SLACK bound) per output {ratios}"
+
+
+def test_emulation_is_exact_on_integers():
+    """the exact regime: the emulated fp32 path gives the integers themselves, past 2048 (where fp16 no longer holds them all)"""
+    M, N, K = HR.WGRAD_MM_CASES[4]
+    dys, xs, d64, x64 = wgrad_case("exact", K, [(M, N)])
+    ref = HR.wgrad(d64[0], x64[0])
+    assert 2048 < float(ref.max()) < 65504
+    _, ktps, _ = HR.split_plan(K, 8)
+    assert torch.equal(HR.emulate_splitk(dys[0], xs[0], ktps, half=False).double(), ref)
+    assert torch.equal(HR.emulate_splitk(dys[0], xs[0], ktps, half=True), ref.half())
+    assert not torch.equal(ref.half().double(), ref)
+
+
+SLIP_MM = HR.WGRAD_MM_CASES[2]                   # 136 x 264 x 1000: the smallest single launch with a split (4 of 4 K-tiles, 24 tail rows)
+SLIP_GROUP = HR.WGRAD_GROUP_CASES["two_f32"]     # the smallest grouped launch with two problems (520 tokens: splits of 5 + 4 K-tiles)
+
+
+@pytest.mark.parametrize("slip", HR.WGRAD_SLIPS)
+def test_slip_wgrad(slip):
+    """every slip of hotpath_ref.wgrad_slipped falls outside the bound in at least one data regime, at the smallest split shape of
+    the single launch (fp16 result) and of the grouped launch (fp32 result).  The slips that only round differently - slab_f16,
+    reduce_f16 - stay inside the bound of an fp16 RESULT by construction (they add roundings of the size the result's own rounding
+    has): they are caught by the fp32 result's bound on same-sign data and, by inequality, in the exact regime
+    (test_slip_wgrad_exact_integers)."""
+    rounding_only = slip in ("slab_f16", "reduce_f16")
+    (M, N, K), (dims, T, _) = SLIP_MM, SLIP_GROUP
+    for what, Tn, shape, s, half, tile in (("single", K, (M, N), 4, True, 128), ("grouped", T, dims[1], 2, False, 256)):
+        _, ktps, splitk = HR.split_plan(Tn, s)
+        assert splitk > 1
+        hit = {}
+        for regime in HR.WGRAD_REGIMES:
+            _, _, d64, x64 = wgrad_case(regime, Tn, [shape])
+            ref, ab = HR.wgrad(d64[0], x64[0]), HR.wgrad(d64[0].abs(), x64[0].abs())
+            bad = HR.wgrad_slipped(d64[0], x64[0], ktps, slip, tile)
+            hit[regime] = HR.detects(ref, bad, HR.wgrad_bound(ref, ab, Tn, ktps, splitk, half))
+        if rounding_only and half:
+            continue
+        assert any(hit.values()), f"{slip} hides inside the {what} bound in both regimes: {hit}"
+        if not rounding_only:
+            assert hit["same"], f"{slip} hides inside the {what} bound on same-sign data"
+
+
+def test_slip_wgrad_group_problem_swapped():
+    dims, T, _ = SLIP_GROUP
+    _, ktps, splitk = HR.split_plan(T, 2)
+    for regime in HR.WGRAD_REGIMES:
+        _, _, d64, x64 = wgrad_case(regime, T, dims)
+        bad = HR.wgrad_group_swapped(d64, x64, ktps)
+        ref0 = HR.wgrad(d64[0], x64[0])
+        assert torch.equal(bad[0], HR.wgrad_partials(d64[0], x64[0], ktps).sum(0)) and float((bad[0] - ref0).abs().max()) < 1e-9
+        ref, ab = HR.wgrad(d64[1], x64[1]), HR.wgrad(d64[1].abs(), x64[1].abs())
+        for half in (True, False):
+            assert HR.detects(ref, bad[1], HR.wgrad_bound(ref, ab, T, ktps, splitk, half)), (regime, half)
+
+
+@pytest.mark.parametrize("slip", ["slab_f16", "reduce_f16"])
+def test_slip_wgrad_exact_integers(slip):
+    """the exact regime's integers over 1000 and more rows: every split's partial passes 2048, an fp16 slab or running sum loses
+    low bits, and the result differs from the exact one - in the fp32 output, and in the fp16 output after its own rounding.  At
+    every shape the GPU tests run this regime on, with the split each gets on 256 CUs."""
+    for (M, N, K), s in ((SLIP_MM, 4), (HR.WGRAD_MM_CASES[3], 4), (HR.WGRAD_MM_CASES[4], 8), (HR.WGRAD_MM_CASES[5], 16), ((768, 256, 2120), 7)):
+        _, ktps, splitk = HR.split_plan(K, s)
+        _, _, d64, x64 = wgrad_case("exact", K, [(M, N)])
+        ref = HR.wgrad(d64[0], x64[0])
+        bad = HR.wgrad_slipped(d64[0], x64[0], ktps, slip)
+        assert float(HR.wgrad_partials(d64[0], x64[0], ktps)[:-1].median()) > 2048 and float(ref.max()) < 65504
+        assert not torch.equal(bad, ref), "fp32 result"
+        assert not torch.equal(bad.half(), ref.half()), "fp16 result"

@@ -44,6 +44,7 @@ def _parse_header(path=HEADER):
 
 
 SIGNATURES, ERRORS, EPI, STATUS = _parse_header()
+TOPN_MAX = int(re.search(r"#define HMMC_TOPN_MAX (\d+)", open(HEADER).read()).group(1))      # longest list of hmmc_topn_select
 
 # The library reads no environment variable itself (include/hmmc_hip.h: hmmc_set_option).  These A/B switches of scratch/ runs
 # and tests are translated once, when the library is loaded; a variable that is PRESENT (any value, the empty string included)

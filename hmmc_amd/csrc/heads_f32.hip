@@ -6,6 +6,7 @@
 //   * temporal pooling  mean_f( (h+u)/||h+u|| )          (modules/module_cross.py:207-212)
 //   * the temporal transformer's F x F fp32 attention    (modules/module_cross.py:127-131)
 //   * the MLM pass's BERT masking of the token ids      (modules/modeling.py:181-205)
+//   * running top-N per row of a score block            (gallery search beside the eval leg; hmmc_amd/search.py)
 // The similarity logits themselves come from hmmc_gemm_f32 as ONE [B, B*(1+F)] matrix
 // S_all = 100 * Qn [Vn ; Un]^T: column c < B is video c, column B + b*F + f is frame f of video b,
 // so the reference's F+1 separate matmuls and 2(F+1) log-softmax passes become one GEMM and three
@@ -506,6 +507,141 @@ __global__ __launch_bounds__(256) void segment_max_kernel(const float* __restric
     for (int s = s0; s < s1; ++s) m = fmaxf(m, S[(long)s * ld + v]);
     out[(long)g * V + v] = m;
   }
+}
+
+// ---------------------------------------------------------------- running top-N per row (gallery search)
+// Streaming selection, one wave (one 64-thread workgroup) per row.  A candidate is the 64-bit key
+//   (~order(score) << 32) | index,   order() = the usual monotone float -> uint32 map,
+// so that ASCENDING key order is (score descending, index ascending as unsigned) and the empty slot (-inf, -1) is the largest
+// key any list can hold.  LDS holds the row's list keys[0, n) and behind it a buffer of survivors: a candidate survives when
+// its key is below the list's n-th key (the threshold), and is appended by ballot + lane prefix.  When the buffer cannot take
+// another 64 survivors, list + buffer are padded to a power of two with empty keys, bitonic-sorted, and the first n are the
+// new list.  Most of a random row never passes the float pre-test in the streaming loop; an ascending row passes everywhere
+// and pays a sort per ~TOPN_KEYS - n columns - slow, and still exact.
+constexpr int TOPN_KEYS = 512;                                   // list + survivor buffer, 4 KiB of LDS per row
+constexpr unsigned long long TOPN_EMPTY = 0xFF800000FFFFFFFFull;  // key of (-inf, -1)
+static_assert(HMMC_TOPN_MAX + 64 <= TOPN_KEYS, "a full list must leave room for one round of 64 survivors");
+
+__device__ __forceinline__ unsigned long long topn_key(float s, unsigned index) {
+  if (!(s == s)) s = -INFINITY;                                  // NaN counts as -inf
+  if (s == 0.f) s = 0.f;                                         // -0 and +0 are one score
+  const unsigned u = __float_as_uint(s);
+  const unsigned ord = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((unsigned long long)(~ord) << 32) | index;
+}
+__device__ __forceinline__ float topn_score(unsigned long long key) {
+  const unsigned ord = ~(unsigned)(key >> 32);
+  return __uint_as_float((ord & 0x80000000u) ? (ord ^ 0x80000000u) : ~ord);
+}
+
+struct TopnRow {
+  unsigned long long* keys;      // LDS [TOPN_KEYS]
+  unsigned long long thresh;     // keys[n - 1]: only smaller keys can enter the list
+  float thresh_score;            // its score: `!(s < thresh_score)` is the streaming loop's cheap, conservative pre-test
+  int n, cnt, limit, lane;       // cnt survivors in keys[n, n + cnt); a sort is due when n + cnt + 64 > limit
+
+  // sort keys[0, n + cnt) ascending, keep the first n (all 64 lanes call this together)
+  __device__ void cut() {
+    const int total = n + cnt;
+    int m = 128;
+    while (m < total) m <<= 1;
+    for (int i = total + lane; i < m; i += 64) keys[i] = TOPN_EMPTY;
+    __syncthreads();
+    for (int k = 2; k <= m; k <<= 1) {
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        for (int t = lane; t < (m >> 1); t += 64) {
+          const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
+          const unsigned long long a = keys[lo], b = keys[hi];
+          if ((a > b) == ((lo & k) == 0)) { keys[lo] = b; keys[hi] = a; }
+        }
+        __syncthreads();
+      }
+    }
+    thresh = keys[n - 1];
+    thresh_score = topn_score(thresh);
+    cnt = 0;
+    limit = TOPN_KEYS;
+  }
+
+  // one candidate per lane (valid lanes only); all 64 lanes call this together
+  __device__ __forceinline__ void consider(float s, unsigned index, bool valid) {
+    const unsigned long long key = topn_key(s, index);
+    const bool in = valid && key < thresh;
+    const unsigned long long mask = __ballot(in);
+    if (mask == 0) return;
+    const int before = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+    if (in) keys[n + cnt + before] = key;
+    cnt += __popcll(mask);
+    if (n + cnt + 64 > limit) cut();
+  }
+};
+
+__global__ __launch_bounds__(64) void topn_select_kernel(const float* __restrict__ S, int cols, long ld, int col_base,
+                                                         float* __restrict__ top_score, int* __restrict__ top_index, int n,
+                                                         int merge) {
+  __shared__ unsigned long long keys[TOPN_KEYS];
+  const int lane = threadIdx.x;
+  const long row = blockIdx.x;
+  float* out_s = top_score + row * n;
+  int* out_i = top_index + row * n;
+  for (int i = lane; i < n; i += 64) keys[i] = merge ? topn_key(out_s[i], (unsigned)out_i[i]) : TOPN_EMPTY;
+  __syncthreads();
+  TopnRow r;
+  r.keys = keys; r.n = n; r.cnt = 0; r.lane = lane;
+  r.thresh = keys[n - 1];
+  r.thresh_score = topn_score(r.thresh);
+  // a short list gets its first threshold after ~64 columns instead of ~500 (a 128-key sort instead of a 512-key one)
+  r.limit = n <= 32 ? 128 : TOPN_KEYS;
+
+  const float* p = S + row * ld;
+  const unsigned base = (unsigned)col_base;          // indices in unsigned arithmetic: lanes past the row's end may wrap
+  // scalar head up to the first 16-byte boundary, 16-byte body, scalar tail
+  int head = (int)(((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) >> 2);
+  head = head < cols ? head : cols;
+  const int nvec = (cols - head) >> 2;
+  const int tail = head + 4 * nvec;
+  r.consider(lane < head ? p[lane] : 0.f, base + lane, lane < head);
+  const f4* pv = reinterpret_cast<const f4*>(p + head);
+  for (int g0 = 0; g0 < nvec; g0 += 256) {
+    f4 v[4];
+    bool pass = false;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int g = g0 + u * 64 + lane;
+      v[u] = g < nvec ? pv[g] : f4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const bool ok = g0 + u * 64 + lane < nvec;
+      pass |= ok && (!(v[u][0] < r.thresh_score) || !(v[u][1] < r.thresh_score) || !(v[u][2] < r.thresh_score) ||
+                     !(v[u][3] < r.thresh_score));
+    }
+    if (__ballot(pass) == 0) continue;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int g = g0 + u * 64 + lane;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) r.consider(v[u][c], base + head + 4 * g + c, g < nvec);
+    }
+  }
+  r.consider(lane < cols - tail ? p[tail + lane] : 0.f, base + tail + lane, lane < cols - tail);
+  if (r.cnt) r.cut();
+  for (int i = lane; i < n; i += 64) {
+    const unsigned long long key = keys[i];
+    out_s[i] = topn_score(key);
+    out_i[i] = (int)(unsigned)key;
+  }
+}
+
+extern "C" int hmmc_topn_select(const float* S, int rows, int cols, long ld, int col_base, float* top_score, int* top_index,
+                                int n, int merge, hipStream_t stream) {
+  if ((!S && cols > 0) || !top_score || !top_index || rows <= 0 || cols < 0 || ld < cols || col_base < 0 || n < 1 ||
+      (long)col_base + cols > 2147483647l)
+    return HMMC_ERR_ARG;
+  if (n > HMMC_TOPN_MAX) return HMMC_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(topn_select_kernel, dim3((unsigned)rows), dim3(64), 0, stream, S, cols, ld, col_base, top_score, top_index,
+                     n, merge);
+  return hmmc_launch_status();
 }
 
 extern "C" int hmmc_segment_max(const float* S, const int* offsets, float* out, int groups, int V, long ld, hipStream_t stream) {

@@ -33,6 +33,22 @@ def compute_metrics_t2v_v2t(sim_matrix):
     return metrics_from_ranks(ranks(sim_matrix)), metrics_from_ranks(ranks(sim_matrix, transposed=True))
 
 
+def recall_from_topn(indices, target=None, ks=(1, 5, 10)):
+    """{"R1": .., "R5": .., "R10": ..} (per cent) from top-N lists [queries, N] (search.Gallery.search, best first): a query
+    counts for K iff its target is among its first K entries; target = an int tensor [queries], None = the diagonal.
+    Median and mean rank need the whole row and are not offered.  On exact ties this can differ from compute_metrics, which
+    counts the candidates scoring STRICTLY higher (the target takes the first of the tied positions): a list orders equal
+    scores by index, so a target tied with lower-indexed candidates sits behind them here."""
+    if indices.dim() != 2:
+        raise ValueError("recall_from_topn: indices must be [queries, N]")
+    if max(ks) > indices.shape[1]:
+        raise ValueError(f"recall_from_topn: R{max(ks)} needs lists of at least {max(ks)} entries, got N = {indices.shape[1]}")
+    if target is None:
+        target = torch.arange(indices.shape[0], device=indices.device)
+    hit = indices.long() == target.to(indices.device).long().view(-1, 1)
+    return {f"R{k}": float(hit[:, :k].any(dim=1).sum()) * 100 / indices.shape[0] for k in ks}
+
+
 # ---- multi-sentence retrieval (several captions per video: MSVD, VATEX) -------------------------------------------------
 
 def _groups(cut_off_points, n_sentences):

@@ -494,6 +494,24 @@ class BirdPreTrainedModel(CLIP4ClipPreTrainedModel):
             out[s:e] = sc if use_frame_fea else sv
         return out
 
+    @torch.no_grad()
+    def build_gallery(self, batch_visual_output_list, batch_frame_output_list, chunk_videos=None):
+        """The candidates of eval_similarity as a resident search.Gallery: packed once (top_frames and the logit scale taken
+        as eval_similarity takes them), queried many times by search(); more videos may be add()-ed to it later."""
+        from .search import Gallery
+        gallery = Gallery(self.top_frames, min(math.exp(float(self.text_encoder.logit_scale)), 100.0), chunk_videos=chunk_videos)
+        gallery.add(torch.cat([t.float() for t in batch_visual_output_list], dim=0),
+                    torch.cat([t.float() for t in batch_frame_output_list], dim=0))
+        return gallery
+
+    @torch.no_grad()
+    def search(self, batch_query_output_list, gallery, topn, use_frame_fea=True, query_chunk=4096):
+        """The topn best videos of every query -> (scores [queries, topn] fp32, indices [queries, topn] int64), best first:
+        the first topn columns of the stable descending sort of eval_similarity's rows, with the same scores, without the
+        [all queries, all videos] matrix (hmmc_eval_score per block + hmmc_topn_select)."""
+        q = torch.cat([t.float() for t in batch_query_output_list], dim=0)
+        return gallery.search(q, topn, use_frame_fea=use_frame_fea, query_chunk=query_chunk)
+
 
 class BirdModel(BirdPreTrainedModel):
     """Fine-tuning model (reference modules/modeling.py:648-722)."""

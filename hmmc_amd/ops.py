@@ -592,11 +592,16 @@ def eval_pack(visual, frames):
     return packed
 
 
-def eval_score(queries_unit, packed, nv, F, k, scale, want=("video", "frame")):
-    """fused scale * Q [V; U]^T -> (video logits, mean top-k frame logits, their sum), each [nq, nv] or None."""
+def eval_score(queries_unit, packed, nv, F, k, scale, want=("video", "frame"), out=None):
+    """fused scale * Q [V; U]^T -> (video logits, mean top-k frame logits, their sum), each [nq, nv] or None.
+    `out`: a contiguous fp32 [nq, nv] tensor that receives the ONE output named by `want` (a caller's reused block)."""
     _chk(queries_unit, torch.float32, "queries_unit")
     nq, E = queries_unit.shape
-    outs = [torch.empty((nq, nv), dtype=torch.float32, device=packed.device) if w in want else None
+    if out is not None:
+        _chk(out, torch.float32, "out")
+        if len(want) != 1 or tuple(out.shape) != (nq, nv) or not out.is_contiguous():
+            raise ValueError("eval_score: `out` takes exactly one wanted output, as a contiguous [nq, nv] tensor")
+    outs = [(out if out is not None else torch.empty((nq, nv), dtype=torch.float32, device=packed.device)) if w in want else None
             for w in ("video", "frame", "score")]
     call("hmmc_eval_score", ptr(queries_unit), ptr(packed), ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), nq, nv, F, E, int(k), float(scale))
     return outs
@@ -610,6 +615,35 @@ def segment_max(sim, offsets):
     out = torch.empty((G, V), dtype=torch.float32, device=sim.device)
     call("hmmc_segment_max", ptr(sim), ptr(offsets), ptr(out), G, V, sim.stride(0))
     return out
+
+
+TOPN_MAX = _lib.TOPN_MAX
+
+
+def topn_select(S, n, col_base=0, out=None):
+    """Running top-n per row of a score block (hmmc_topn_select): S [rows, cols] fp32 with unit column stride (rows may be
+    strided and unaligned), column j = candidate col_base + j -> (top_score [rows, n] fp32, top_index [rows, n] int32), sorted
+    by (score descending, index ascending); slots without a candidate hold (-inf, -1).  `out=(top_score, top_index)`: lists of
+    earlier calls, merged with this block's candidates in place and returned."""
+    if S.dtype != torch.float32 or not S.is_cuda:                       # as _chk, which also asks for contiguous rows
+        raise TypeError(f"S: expected cuda {torch.float32}, got {S.device} {S.dtype}")
+    if S.dim() != 2 or (S.shape[1] > 1 and S.stride(1) != 1):
+        raise ValueError("topn_select: S must be [rows, cols] with unit column stride")
+    rows, cols = S.shape
+    ld = S.stride(0) if rows > 1 else max(S.stride(0), cols)
+    if out is None:
+        top_score = torch.empty((rows, int(n)), dtype=torch.float32, device=S.device)
+        top_index = torch.empty((rows, int(n)), dtype=torch.int32, device=S.device)
+    else:
+        top_score, top_index = out
+        _chk(top_score, torch.float32, "top_score")
+        _chk(top_index, torch.int32, "top_index")
+        if tuple(top_score.shape) != (rows, n) or tuple(top_index.shape) != (rows, n) or not top_score.is_contiguous() \
+                or not top_index.is_contiguous():
+            raise ValueError(f"topn_select: out must be two contiguous [{rows}, {n}] tensors")
+    call("hmmc_topn_select", ptr(S) if cols else None, rows, cols, ld, int(col_base), ptr(top_score), ptr(top_index), int(n),
+         int(out is not None))
+    return top_score, top_index
 
 
 def retrieval_rank(sim, target=None, transposed=False):

@@ -279,6 +279,21 @@ int hmmc_retrieval_rank(const float* S, const int* target, int* rank, int Q, int
  * sentences offsets[g] <= s < offsets[g+1] of S[s][v] (NaN counts as -inf); offsets is a device int32 [groups + 1].
  * Rank it with hmmc_retrieval_rank(transposed = 1). */
 int hmmc_segment_max(const float* S, const int* offsets, float* out, int groups, int V, long ld, hmmc_stream_t stream);
+/* Gallery search (the text-to-video search the reference's README links as its demo; the reference itself only ranks one known
+ * target per query): running top-N per row of a score block.  S [rows][ld] fp32, columns 0..cols-1 valid (cols = 0: no
+ * candidates, S may be NULL); column j is candidate col_base + j.
+ * top_score / top_index: [rows][n] fp32 / int32, sorted by (score descending, index ascending).
+ * merge = 0: lists are formed from this block alone.
+ * merge = 1: the lists already in top_score / top_index (sorted, from earlier calls) are merged with this block's candidates.
+ * (score, index) is a total order and an index occurs at most once in a search, so the lists after any sequence of calls
+ * depend only on the set of candidates seen, not on how the columns were cut into blocks or on the blocks' order.
+ * NaN counts as -inf; -0 counts as, and is returned as, +0.  A real candidate with score -inf still precedes an empty slot.
+ * Empty slots (fewer than n candidates so far) hold score -inf and index -1, after every real candidate.
+ * 1 <= n <= HMMC_TOPN_MAX; larger n: HMMC_ERR_UNSUPPORTED.  ld >= cols, col_base >= 0, col_base + cols <= INT_MAX.
+ * S and ld need no alignment.  No atomics: bit-identical from run to run. */
+#define HMMC_TOPN_MAX 128
+int hmmc_topn_select(const float* S, int rows, int cols, long ld, int col_base, float* top_score, int* top_index, int n,
+                     int merge, hmmc_stream_t stream);
 /* Eval scorer (main_task_retrieval.py:321-357 _run_on_single_gpu; modules/modeling.py:207-229 loose_similarity):
  * hmmc_eval_slots(F) = rows per video of the packed candidate matrix (16 or 32; 0: F + 1 > 32, use hmmc_gemm_f32 +
  * hmmc_topk_mean).  hmmc_eval_pack writes packed [nv * slots][E]: slot 0 = visual[v] / |visual[v]|, slots 1..F =

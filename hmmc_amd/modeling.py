@@ -505,12 +505,13 @@ class BirdPreTrainedModel(CLIP4ClipPreTrainedModel):
         return gallery
 
     @torch.no_grad()
-    def search(self, batch_query_output_list, gallery, topn, use_frame_fea=True, query_chunk=4096):
+    def search(self, batch_query_output_list, gallery, topn, use_frame_fea=True, query_chunk=4096, frames=False):
         """The topn best videos of every query -> (scores [queries, topn] fp32, indices [queries, topn] int64), best first:
         the first topn columns of the stable descending sort of eval_similarity's rows, with the same scores, without the
-        [all queries, all videos] matrix (hmmc_eval_score per block + hmmc_topn_select)."""
+        [all queries, all videos] matrix (hmmc_eval_score per block + hmmc_topn_select).  frames=True adds, for every hit, its
+        top_frames best frame logits and their frame numbers (hmmc_hit_frames): (scores, indices, frame_scores, frame_indices)."""
         q = torch.cat([t.float() for t in batch_query_output_list], dim=0)
-        return gallery.search(q, topn, use_frame_fea=use_frame_fea, query_chunk=query_chunk)
+        return gallery.search(q, topn, use_frame_fea=use_frame_fea, query_chunk=query_chunk, frames=frames)
 
 
 class BirdModel(BirdPreTrainedModel):

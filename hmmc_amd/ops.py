@@ -646,6 +646,48 @@ def topn_select(S, n, col_base=0, out=None):
     return top_score, top_index
 
 
+def hit_frames(queries_unit, packed, count, F, k, scale, pair_query, pair_video, video_base=0, out=None, want_video=False):
+    """The k best frames of given (query, video) pairs (hmmc_hit_frames): queries_unit [nq, E], packed = one eval_pack chunk of
+    `count` videos with the global indices video_base .. video_base + count - 1, pair_query / pair_video int32 of one shape
+    [...] -> (frame_score [..., k] fp32, frame_index [..., k] int32), ordered by (logit descending, frame ascending), and with
+    want_video a third tensor, the video logit [...].  A pair whose query or video lies outside the chunk (-1: an empty list
+    slot) keeps what its outputs held: (-inf, -1) and NaN when they are allocated here, the caller's values with
+    `out=(frame_score, frame_index[, video_logit])`, tensors of earlier calls on other chunks."""
+    _chk(queries_unit, torch.float32, "queries_unit")
+    _chk(packed, torch.float32, "packed")
+    _chk(pair_query, torch.int32, "pair_query")
+    _chk(pair_video, torch.int32, "pair_video")
+    if queries_unit.dim() != 2 or packed.dim() != 2 or packed.shape[1] != queries_unit.shape[1]:
+        raise ValueError(f"hit_frames: queries_unit [nq, E] and packed [rows, E], got {tuple(queries_unit.shape)} and {tuple(packed.shape)}")
+    nq, E = queries_unit.shape
+    if packed.shape[0] != int(count) * eval_slots(F):
+        raise ValueError(f"hit_frames: packed holds {packed.shape[0]} rows, {count} videos of F = {F} take {int(count) * eval_slots(F)}")
+    if pair_query.shape != pair_video.shape:
+        raise ValueError("hit_frames: pair_query and pair_video must have one shape")
+    shape, k = tuple(pair_query.shape), int(k)
+    if out is None:
+        frame_score = torch.full(shape + (k,), float("-inf"), dtype=torch.float32, device=packed.device)
+        frame_index = torch.full(shape + (k,), -1, dtype=torch.int32, device=packed.device)
+        video = torch.full(shape, float("nan"), dtype=torch.float32, device=packed.device) if want_video else None
+    else:
+        frame_score, frame_index = out[0], out[1]
+        video = out[2] if len(out) > 2 else None
+        if want_video and video is None:
+            raise ValueError("hit_frames: want_video with `out` takes the video logits as out[2]")
+        _chk(frame_score, torch.float32, "frame_score")
+        _chk(frame_index, torch.int32, "frame_index")
+        if tuple(frame_score.shape) != shape + (k,) or tuple(frame_index.shape) != shape + (k,):
+            raise ValueError(f"hit_frames: out must hold two contiguous {list(shape + (k,))} tensors")
+        if video is not None:
+            _chk(video, torch.float32, "video_logit")
+            if tuple(video.shape) != shape:
+                raise ValueError(f"hit_frames: out[2] must be a contiguous {list(shape)} tensor")
+    if pair_query.numel():                                               # an empty tensor has no pointer to hand over
+        call("hmmc_hit_frames", ptr(queries_unit), ptr(packed), ptr(pair_query), ptr(pair_video), ptr(frame_score),
+             ptr(frame_index), ptr(video), pair_query.numel(), nq, int(count), int(video_base), int(F), E, k, float(scale))
+    return (frame_score, frame_index, video) if video is not None else (frame_score, frame_index)
+
+
 def retrieval_rank(sim, target=None, transposed=False):
     """rank[q] = #{j : S(q, j) > S(q, target[q])} (int32); S(q, j) = sim[q, j], or sim[j, q] with transposed."""
     _chk(sim, torch.float32, "sim")

@@ -5,7 +5,8 @@ need in full.  A search needs the N best candidates of every query only, so here
 [query chunk x gallery chunk] block is scored by the fused eval scorer exactly as eval_similarity scores it
 (ops.eval_score), folded into running per-query lists by one streaming pass (ops.topn_select), and overwritten by the next
 block.  The order of a list is (score descending, index ascending), a total order, so the result does not depend on how the
-gallery or the queries were cut."""
+gallery or the queries were cut.  With frames=True a search also says where in each hit the match is: once the lists are
+final, ops.hit_frames gathers the top_frames best frame logits of every (query, hit) pair and their frame numbers."""
 import torch
 
 from . import ops
@@ -90,14 +91,30 @@ class Gallery:
         ops.eval_score(qn, self.chunks[c], self.counts[c], self.F, self.top_frames, self.scale,
                        want=("score",) if use_frame_fea else ("video",), out=block)
 
+    def _frame_lists(self, rows, topn, device):
+        return (torch.full((rows, topn, self.top_frames), float("-inf"), dtype=torch.float32, device=device),
+                torch.full((rows, topn, self.top_frames), -1, dtype=torch.int32, device=device))
+
+    def _hit_frames(self, qn, c, base, pair_query, pair_video, out):
+        """fill `out` for the pairs whose video lies in chunk c (videos base .. base + counts[c] - 1); the others keep theirs"""
+        ops.hit_frames(qn, self.chunks[c], self.counts[c], self.F, self.top_frames, self.scale, pair_query, pair_video,
+                       video_base=base, out=out)
+
     @torch.no_grad()
-    def search(self, queries, topn, use_frame_fea=True, query_chunk=4096):
+    def search(self, queries, topn, use_frame_fea=True, query_chunk=4096, frames=False):
         """text -> video: for every row of queries [nq, E] its topn videos -> (scores [nq, topn] fp32, indices [nq, topn]
-        int64), best first, ties by index; (-inf, -1) past the end of a gallery smaller than topn.  Stays on the device."""
+        int64), best first, ties by index; (-inf, -1) past the end of a gallery smaller than topn.  Stays on the device.
+        frames=True -> (scores, indices, frame_scores [nq, topn, top_frames] fp32, frame_indices, the same shape, int64): for
+        the hit indices[r, j] its top_frames largest frame logits and their frame numbers, best first, ties by frame number -
+        the terms whose mean the score adds to the video logit; (-inf, -1) in an empty slot.  They are gathered once a query
+        chunk's lists are final (ops.hit_frames, one call per gallery chunk); with use_frame_fea=False the lists are ranked by
+        the video logit alone and the frames are still those of each hit."""
         topn, query_chunk = int(topn), int(query_chunk)
         self._check(queries, topn)
         nq, dev = queries.shape[0], queries.device
         score, index = self._lists(nq, topn, dev)
+        if frames:
+            frame_score, frame_index = self._frame_lists(nq, topn, dev)
         q = queries.float().contiguous()
         rows = min(query_chunk, nq)
         buf = self._buffer("block", rows * max(self.counts, default=0), dev)
@@ -110,18 +127,31 @@ class Gallery:
                 self._score(block, qn, c, use_frame_fea)
                 ops.topn_select(block, topn, col_base=base, out=lists)
                 base += count
+            if frames:
+                pair_query = torch.arange(q1 - q0, dtype=torch.int32, device=dev)[:, None].expand(q1 - q0, topn).contiguous()
+                base = 0
+                for c, count in enumerate(self.counts):
+                    self._hit_frames(qn, c, base, pair_query, index[q0:q1], (frame_score[q0:q1], frame_index[q0:q1]))
+                    base += count
+        if frames:
+            return score, index.long(), frame_score, frame_index.long()
         return score, index.long()
 
     @torch.no_grad()
-    def search_texts(self, queries, topn, use_frame_fea=True, query_chunk=4096):
+    def search_texts(self, queries, topn, use_frame_fea=True, query_chunk=4096, frames=False):
         """video -> text: for every gallery video the topn rows of queries, same score -> (scores [len(g), topn] fp32,
-        indices [len(g), topn] int64).  Each scored block is transposed into a second reused buffer and selected row-wise."""
+        indices [len(g), topn] int64).  Each scored block is transposed into a second reused buffer and selected row-wise.
+        frames=True adds frame_scores / frame_indices [len(g), topn, top_frames] as search() does: entry [v, j] holds the best
+        frames of video v for the query indices[v, j].  The unit queries are resident whole here, so the gather is one
+        ops.hit_frames call per gallery chunk."""
         topn, query_chunk = int(topn), int(query_chunk)
         self._check(queries, topn)
         nq, dev = queries.shape[0], queries.device
         score, index = self._lists(len(self), topn, dev)
+        if frames:
+            frame_score, frame_index = self._frame_lists(len(self), topn, dev)
         if nq == 0:
-            return score, index.long()
+            return (score, index.long(), frame_score, frame_index.long()) if frames else (score, index.long())
         qn, _ = ops.l2norm_fwd(queries.float().contiguous())
         rows = min(query_chunk, nq)
         most = rows * max(self.counts, default=0)
@@ -137,4 +167,12 @@ class Gallery:
                 turned.copy_(block.t())
                 ops.topn_select(turned, topn, col_base=q0, out=lists)
             base += count
+        if frames:
+            base = 0
+            for c, count in enumerate(self.counts):
+                pair_video = torch.arange(base, base + count, dtype=torch.int32, device=dev)[:, None].expand(count, topn).contiguous()
+                self._hit_frames(qn, c, base, index[base:base + count], pair_video,
+                                 (frame_score[base:base + count], frame_index[base:base + count]))
+                base += count
+            return score, index.long(), frame_score, frame_index.long()
         return score, index.long()

@@ -305,6 +305,25 @@ int hmmc_eval_slots(int F);
 int hmmc_eval_pack(const float* visual, const float* frames, float* packed, int nv, int F, int E, hmmc_stream_t stream);
 int hmmc_eval_score(const float* queries_unit, const float* packed, float* out_video, float* out_frame, float* out_score,
                     int nq, int nv, int F, int E, int k, float scale, hmmc_stream_t stream);
+/* The frames behind a search hit: the k largest frame logits of given (query, video) pairs and the frames they belong to - the
+ * terms whose mean hmmc_eval_score adds to the video logit (main_task_retrieval.py:334-336 torch.topk over the frame axis of
+ * the frame logits of modules/modeling.py:225-227) and then drops.  A gather: pairs out of nq * nv, (F + 1) * E * 4 bytes each.
+ * packed: ONE chunk as hmmc_eval_pack writes it, [nv * hmmc_eval_slots(F)][E]; its videos are the global indices video_base ..
+ * video_base + nv - 1.  queries_unit [nq][E] is taken as given.  Pair m: q = pair_query[m], v = pair_video[m] - video_base.
+ * q outside 0..nq-1 or v outside 0..nv-1 (-1 = an empty list slot): the pair's outputs are left untouched, so a caller
+ * pre-fills them and calls once per chunk.  Otherwise logit_f = scale * sum_e q[e] * packed[(v * P + 1 + f) * E + e], f < F;
+ * frame_score / frame_index [pairs][k] receive the k largest and their f, ordered by (logit descending, f ascending), a total
+ * order.  NaN counts as, and is returned as, -inf; -0 is returned as +0 (the conventions of hmmc_topn_select).
+ * video_logit [pairs] (may be NULL) = scale * q . slot 0, as computed.
+ * Summation order of a logit (fixed): lane l of the pair's wave adds the elements e = 256 j + 4 l + c, j ascending and inside j
+ * c = 0..3, by fused multiply-add from 0; the 64 lane sums are added by the butterfly s += s(lane ^ o), o = 32, 16, 8, 4, 2, 1;
+ * the total is multiplied by scale.  No atomics; a pair's result depends on its two rows only - not on its position, on the
+ * other pairs or on how the gallery was cut into chunks - and is bit-identical from run to run.
+ * HMMC_ERR_ARG: a null required pointer, k outside 1..F, negative counts, E <= 0.  HMMC_ERR_UNSUPPORTED, as hmmc_eval_pack:
+ * hmmc_eval_slots(F) == 0, E % 4 != 0, queries_unit / packed not 16-byte aligned.  pairs == 0: success, nothing launched. */
+int hmmc_hit_frames(const float* queries_unit, const float* packed, const int* pair_query, const int* pair_video,
+                    float* frame_score, int* frame_index, float* video_logit, long pairs, int nq, int nv,
+                    int video_base, int F, int E, int k, float scale, hmmc_stream_t stream);
 
 /* video_emb[b] = mean_f (h + u)/||h + u||  (modules/module_cross.py:207-212); u may be NULL (use_temp False). */
 int hmmc_temporal_pool_fwd(const float* h, const float* u, float* out, float* norms, int b, int F, int D,

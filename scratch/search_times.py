@@ -6,6 +6,10 @@ variants alternated A-B-C-C-B-A in one process; median and min over the rounds, 
   (b) model.search(topn = 10) against eval_similarity + torch.topk(sim, 10) at 15 000 x 1 500 x 24 (bench.py --mode eval
       --frames 24), same process, same inputs
 
+  (c) Gallery.search(frames=True) against Gallery.search() at 4 096 queries x 1 500 videos, topn 10 and 128, F 12 and 24:
+      the added time, and the gathered bytes per second pairs * (F + 1) * E * 4 / t over it and over the hmmc_hit_frames
+      launch alone on the final lists
+
     python scratch/search_times.py [--rounds 5] [--reps 20] [--out FILE]"""
 import argparse
 import json
@@ -105,6 +109,30 @@ def search_vs_eval(rounds, reps, emit):
     emit({"what": "whole search vs eval_similarity + torch.topk(sim, 10)", "size": [nq, nv, F], "scores_equal": same, **res})
 
 
+def frames_vs_plain_search(nq, nv, F, topn, rounds, reps, emit):
+    from hmmc_amd.search import Gallery
+    E, k = 512, 3
+    gen = torch.Generator(device=DEV).manual_seed(2)
+    q = torch.randn(nq, E, device=DEV, generator=gen)
+    gallery = Gallery(k, 100.0)
+    gallery.add(torch.randn(nv, E, device=DEV, generator=gen), torch.randn(nv, F, E, device=DEV, generator=gen))
+    qn, _ = ops.l2norm_fwd(q)
+    _, index = gallery.search(q, topn)
+    pair_video = index.int().contiguous()
+    pair_query = torch.arange(nq, dtype=torch.int32, device=DEV)[:, None].expand(nq, topn).contiguous()
+    out = ops.hit_frames(qn, gallery.chunks[0], nv, F, k, 100.0, pair_query, pair_video)
+    res = alternate({"search": lambda: gallery.search(q, topn), "search_frames": lambda: gallery.search(q, topn, frames=True),
+                     "hit_frames_launch": lambda: ops.hit_frames(qn, gallery.chunks[0], nv, F, k, 100.0, pair_query, pair_video, out=out)},
+                    rounds, reps)
+    gathered = nq * topn * (F + 1) * E * 4
+    added = res["search_frames"]["median_ms"] - res["search"]["median_ms"]
+    emit({"what": "search(frames=True) vs search()", "size": [nq, nv, F], "topn": topn, "pairs": nq * topn,
+          "gathered_MB": round(gathered / 1e6, 1), "added_ms": round(added, 4),
+          "added_share_of_search": round(added / res["search"]["median_ms"], 4),
+          "GB_per_s_over_added": round(gathered / added / 1e6, 1) if added > 0 else None,
+          "GB_per_s_over_launch": round(gathered / res["hit_frames_launch"]["median_ms"] / 1e6, 1), **res})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
@@ -123,6 +151,9 @@ def main():
     select_vs_scorer(4096, 1500, 24, args.rounds, args.reps, emit)
     select_vs_scorer(4096, 16384, 12, args.rounds, max(2, args.reps // 4), emit)
     search_vs_eval(args.rounds, args.reps, emit)
+    for F in (12, 24):
+        for topn in (10, 128):
+            frames_vs_plain_search(4096, 1500, F, topn, args.rounds, args.reps, emit)
 
 
 if __name__ == "__main__":
